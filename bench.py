@@ -9,8 +9,10 @@ One step = one pass of the hot path over one batch resident in HBM:
     python bench.py [--gpus N] [--steps K] [--warmup W]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line with the driver's contract fields plus "roofline" (dominant kernel,
-HIP-event timed inside the timed region) and "cpu_baseline" (the oracle timed on the host cores).
+Rank 0 prints ONE JSON line with the driver's contract fields.  A plain run sets up, warms up, times exactly K steps
+(one timed region), writes the last step's outputs if --dump-outputs is given and prints the line.  With --full the line
+also carries "roofline" (dominant kernel, HIP-event timed inside the timed region), "cpu_baseline" (the oracle timed on
+the host cores) and "legs" (the other workloads), and the headline is the median of R >= 20 timed regions of K steps.
 """
 import argparse
 import ctypes
@@ -57,11 +59,25 @@ def parse():
                     help="(internal) one rank of the N > 1 legs: started by the ranks of a `--gpus N` run after their headline "
                          "regions, on a process group of its own; rank 0 prints the legs' JSON")
     ap.add_argument("--replays", type=int, default=0,
-                    help="timed regions of K steps each (0: as many as give >= 0.25 s of timed work, at least 20)")
+                    help="timed regions of K steps each (0: one region of exactly K steps after untimed ones for >= 0.25 s "
+                         "of work; with --full as many as give >= 0.25 s of timed work, at least 20); ms_per_step is the "
+                         "median region over K")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: repeated timed regions, roofline and per-kernel timings, "
+                         "the gradient step's eager phases, CPU baselines (unless --no-cpu-baseline), the secondary legs at "
+                         "N = 1 and the collective legs at N > 1 (unless --no-legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(rank 0; float32 / float64; a fixed, seeded sample of rows above 64 MB in all)")
     return ap.parse_args()
 
 
 COLL_DEV = None   # device of the timing collectives' tensors (set in main)
+
+
+def settle_before_capture(dev):
+    from inverse_audio_synthesis_amd.dist import settle_before_capture as settle
+    settle(dev)
 
 
 def spawn_ranks(n):
@@ -133,7 +149,8 @@ MFMA_BF16_PEAK_TFLOPS = 2500.0   # dense bf16 MFMA peak of MI355X (MI355X_MICROA
 
 
 def timed_regions(one_region_fn, args, world, dev):
-    """R timed regions of exactly K steps each (barrier + synchronize on both sides, max over ranks); -> sorted list."""
+    """R timed regions of exactly K steps each (barrier + synchronize on both sides, max over ranks); -> sorted list
+    (a plain run: one)."""
     def sync_all():
         torch.cuda.synchronize()
         if world > 1:
@@ -153,12 +170,48 @@ def timed_regions(one_region_fn, args, world, dev):
         return el
 
     first = one()
-    replays = args.replays if args.replays > 0 else max(20, min(2000, int(0.25 / max(first, 1e-6)) + 1))
+    plain = not args.full and args.replays <= 0
+    # a plain run times ONE region of exactly K steps, after as many regions as --full would time (>= 0.25 s of work, each
+    # between the same brackets) that it does not report: the first regions after a capture run up to ~0.6 ms longer
+    # (+20 % per step at K = 20) than the steady state that the median of --full measures
+    replays = args.replays if args.replays > 0 else max(0 if plain else 20, min(2000, int(0.25 / max(first, 1e-6)) + 1))
     if world > 1:
         r = torch.tensor([replays], dtype=torch.int64, device=COLL_DEV)
         dist.broadcast(r, 0)
         replays = int(r.item())
+    if plain:
+        for _ in range(replays):
+            one()
+        return [one()]
     return sorted(one() for _ in range(replays))
+
+
+DUMP_BYTES = 64 * 10**6      # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy, float32 (float64 stays float64).  When the arrays hold more than
+    DUMP_BYTES in all, every array with more than one row keeps the same fraction of its rows (first dimension), chosen by a
+    generator seeded with `seed` and kept in ascending order: arrays with the same number of rows keep the same rows, and
+    two runs with the same arguments keep the same ones."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    fixed = sum(a.nbytes for a in host.values() if a.ndim == 0 or a.shape[0] <= 1)
+    scalable = sum(a.nbytes for a in host.values() if a.ndim > 0 and a.shape[0] > 1)
+    if fixed + scalable > DUMP_BYTES:
+        keep = (DUMP_BYTES - fixed) / scalable
+        for name, a in host.items():
+            if a.ndim > 0 and a.shape[0] > 1:
+                k = max(1, int(a.shape[0] * keep))
+                rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], k, replace=False))
+                host[name] = np.ascontiguousarray(a[rows])
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in host.items()}
 
 
 def vicreg_cpu_baseline(B, D):
@@ -236,7 +289,7 @@ def run_vicreg(args, rank, world, dev):
 
     for _ in range(max(args.warmup, 2)):
         step()
-    torch.cuda.synchronize()
+    settle_before_capture(dev)
     launch, graph = "eager", None
     # the K steps replay from one hipGraph -- with the gather too when the collectives are RCCL's (they capture like any
     # other stream work; a gloo rehearsal stays eager)
@@ -267,12 +320,31 @@ def run_vicreg(args, rank, world, dev):
     regions = timed_regions(region, args, world, dev)
     elapsed = regions[len(regions) // 2]
     out = [float(v) for v in state["out"]]
+    Bg = B * world
+    result = {
+        "metric": "VICReg.loss forward+backward, embeddings [B, 8192] per GPU (BASELINE configs[2]; N>1: configs[3] with "
+                  "the FullGatherLayer all-gather / reduce-scatter over RCCL)",
+        "value": round(world * B * args.steps / elapsed, 1), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "ms_per_step_min": round(regions[0] / args.steps * 1e3, 4), "timed_regions": len(regions),
+        "timed_region_s": round(elapsed, 5), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16 MFMA Gram (fp32 centring and accumulation), fp32 elsewhere", "data": "synthetic",
+        "config": {"workload": f"VICReg.loss fwd+bwd, x, y = randn({B}, {D}) per rank, global batch {Bg}",
+                   "batch_per_gpu": B, "embeddim": D, "launch": launch, "gather": gather,
+                   "collective": "all_gather_into_tensor fwd + reduce_scatter_tensor bwd (RCCL)" if gather else None,
+                   "rccl_world_size": dist.get_world_size() if gather else 1,
+                   "loss": out[0], "repr_loss": out[1], "std_loss": out[2], "cov_loss": out[3]},
+    }
+    if args.dump_outputs and rank == 0:
+        names = ("loss", "repr_loss", "std_loss", "cov_loss")
+        dump_outputs(args.dump_outputs, dict(zip(names, state["out"]), grad_x=state["grads"][0], grad_y=state["grads"][1]))
+    if not args.full:
+        return result
 
     # ---- the covariance contraction alone (stage 1 of ias_vicreg_stage on a filled workspace), HIP events around K launches.
     # The product path contracts over the batch where the padded batch <= D (B x B matrix, 2 B^2 D flops: SURVEY 8(d)'s
     # identity); the feature-side D x D kernels of rounds 1-3 (2 B D^2 flops) are timed next to it through the diagnostic
     # library under ias_vicreg_set_form(0), and the whole forward + backward once more in that form: `roofline.dxd`.
-    Bg = B * world
     xg = torch.randn(Bg, D, generator=torch.Generator().manual_seed(100)).to(dev)
     yg = torch.randn(Bg, D, generator=torch.Generator().manual_seed(101)).to(dev)
     need = int(lib.ias_vicreg_workspace_bytes(Bg, D))
@@ -354,21 +426,8 @@ def run_vicreg(args, rank, world, dev):
         executed, kernel = executed_dxd, dxd_name
     achieved = executed / (gram_ms * 1e-3) / 1e12
     step_bytes = 16.0 * B * D                                                 # read x, y; write gx, gy (fp32), per rank
-    result = {
-        "metric": "VICReg.loss forward+backward, embeddings [B, 8192] per GPU (BASELINE configs[2]; N>1: configs[3] with "
-                  "the FullGatherLayer all-gather / reduce-scatter over RCCL)",
-        "value": round(world * B * args.steps / elapsed, 1), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "ms_per_step_min": round(regions[0] / args.steps * 1e3, 4), "timed_regions": len(regions),
-        "timed_region_s": round(elapsed, 5), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "bf16 MFMA Gram (fp32 centring and accumulation), fp32 elsewhere", "data": "synthetic",
-        "config": {"workload": f"VICReg.loss fwd+bwd, x, y = randn({B}, {D}) per rank, global batch {Bg}",
-                   "batch_per_gpu": B, "embeddim": D, "launch": launch, "gather": gather,
-                   "collective": "all_gather_into_tensor fwd + reduce_scatter_tensor bwd (RCCL)" if gather else None,
-                   "rccl_world_size": dist.get_world_size() if gather else 1,
-                   "loss": out[0], "repr_loss": out[1], "std_loss": out[2], "cov_loss": out[3]},
-        "roofline": vicreg_roofline(batch_side, kernel, achieved, gram_ms, executed, nominal, kpad, step_bytes, elapsed / args.steps, dxd),
-    }
+    result["roofline"] = vicreg_roofline(batch_side, kernel, achieved, gram_ms, executed, nominal, kpad, step_bytes,
+                                         elapsed / args.steps, dxd)
     if rank == 0 and not args.no_cpu_baseline and world == 1:
         result["cpu_baseline"] = vicreg_cpu_baseline(B, D)
     return result
@@ -383,6 +442,7 @@ def secondary_legs(args, dev):
                                    ("gradstep", "gradstep", 64, 5)):
         a2 = copy.copy(args)
         a2.workload, a2.batch, a2.steps, a2.warmup, a2.replays, a2.no_cpu_baseline = wl, batch, steps, 2, 10, True
+        a2.full, a2.dump_outputs = True, None        # a leg reports its roofline; only the headline dumps
         t0 = time.perf_counter()
         try:
             r = (run_vicreg if wl == "vicreg" else run_gradstep)(a2, 0, 1, dev)
@@ -532,6 +592,7 @@ def vicreg_gather_leg(args, rank, world, dev):
     import copy
     a2 = copy.copy(args)
     a2.workload, a2.batch, a2.steps, a2.warmup, a2.replays, a2.no_cpu_baseline = "vicreg", 128, 10, 2, 10, True
+    a2.full, a2.dump_outputs = True, None        # a leg reports its roofline; only the headline dumps
     r = run_vicreg(a2, rank, world, dev)
     leg = {k: r[k] for k in ("ms_per_step", "ms_per_step_min", "steps", "timed_regions", "value", "unit")}
     leg.update(workload=r["config"]["workload"], launch=r["config"]["launch"], collective=r["config"]["collective"],
@@ -639,6 +700,7 @@ def gradstep_all_ranks_leg(args, rank, world, dev):
     import copy
     a2 = copy.copy(args)
     a2.workload, a2.batch, a2.steps, a2.warmup, a2.replays, a2.no_cpu_baseline = "gradstep", 64, 5, 2, 10, True
+    a2.full, a2.dump_outputs = True, None        # a leg reports its roofline; only the headline dumps
     r = run_gradstep(a2, rank, world, dev)
     return {"ms_per_step": r["ms_per_step"], "ms_per_step_min": r["ms_per_step_min"], "steps": r["steps"],
             "timed_regions": r["timed_regions"], "value": r["value"], "unit": r["unit"], "n_gpus": world,
@@ -830,7 +892,7 @@ def run_gradstep(args, rank, world, dev):
 
     for _ in range(max(args.warmup, 2)):
         step()
-    torch.cuda.synchronize()
+    settle_before_capture(dev)
     launch, graph = "eager", None
     if not args.no_graph:
         try:
@@ -857,20 +919,8 @@ def run_gradstep(args, rank, world, dev):
 
     regions = timed_regions(region, args, world, dev)
     elapsed = regions[len(regions) // 2]
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-    step(ev)
-    torch.cuda.synchronize()
-    phases = [ev[i].elapsed_time(ev[i + 1]) for i in range(3)]
-    gnorm = float(state["g"].norm())
-    # algorithmic HBM bytes of the step per audio sample (SURVEY.md 8d): render 8 (noise in, audio out); PQMF analysis
-    # 8 (4 in + 4 out); each STFT resolution 4 in + 4 (n_fft/2+1)/hop target read; backward: the cotangent of the audio
-    # written and read once per loss (4 x 4 x 2), the render backward reads noise + cotangent (8)
-    bins = sum((n // 2 + 1) / h for n, h in ((1024, 120), (2048, 240), (512, 50)))
-    bytes_per_sample = 8 + 8 + 3 * 4 + 4 * bins + 32 + 8
-    algo = bytes_per_sample * B * T
     ms = elapsed / args.steps * 1e3
-    pipes = gradstep_pipes(ms, B)
-    return {
+    result = {
         "metric": "audio-seconds rendered+lossed+differentiated/sec, BASELINE configs[4] per-GPU share: 64-band PQMF + "
                   "3-resolution STFT loss, forward + backward to the 78 parameters",
         "value": round(world * B * SECONDS * args.steps / elapsed, 1), "unit": "audio-s/s", "n_gpus": world,
@@ -880,14 +930,30 @@ def run_gradstep(args, rank, world, dev):
         "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"BASELINE configs[4] share: grad step, batch {B} x {SECONDS:g} s @ {SAMPLE_RATE} Hz per GPU, "
                                "PQMF(64) sub-band L1 + MR-STFT (1024/2048/512)", "batch_per_gpu": B, "launch": launch,
-                   "loss": float(state["loss"]), "grad_norm": gnorm,
-                   "phase_ms_eager": {"render_forward": round(phases[0], 4), "losses_forward": round(phases[1], 4),
-                                      "backward": round(phases[2], 4)}},
-        "roofline": {"kernel": "whole gradient step (no single dominant kernel: ~20 launches)", "bound": "hbm",
-                     "achieved": round(algo / (ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(algo / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": None, "pipes": pipes,
-                     "algorithmic_bytes_per_step": int(algo), "bytes_per_sample": round(bytes_per_sample, 1)},
+                   "loss": float(state["loss"]), "grad_norm": float(state["g"].norm())},
     }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": state["loss"], "grad_params": state["g"]})
+    if not args.full:
+        return result
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    step(ev)
+    torch.cuda.synchronize()
+    phases = [ev[i].elapsed_time(ev[i + 1]) for i in range(3)]
+    result["config"]["phase_ms_eager"] = {"render_forward": round(phases[0], 4), "losses_forward": round(phases[1], 4),
+                                          "backward": round(phases[2], 4)}
+    # algorithmic HBM bytes of the step per audio sample (SURVEY.md 8d): render 8 (noise in, audio out); PQMF analysis
+    # 8 (4 in + 4 out); each STFT resolution 4 in + 4 (n_fft/2+1)/hop target read; backward: the cotangent of the audio
+    # written and read once per loss (4 x 4 x 2), the render backward reads noise + cotangent (8)
+    bins = sum((n // 2 + 1) / h for n, h in ((1024, 120), (2048, 240), (512, 50)))
+    bytes_per_sample = 8 + 8 + 3 * 4 + 4 * bins + 32 + 8
+    algo = bytes_per_sample * B * T
+    pipes = gradstep_pipes(ms, B)
+    result["roofline"] = {"kernel": "whole gradient step (no single dominant kernel: ~20 launches)", "bound": "hbm",
+                          "achieved": round(algo / (ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": round(algo / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": None, "pipes": pipes,
+                          "algorithmic_bytes_per_step": int(algo), "bytes_per_sample": round(bytes_per_sample, 1)}
+    return result
 
 
 def main():
@@ -1070,7 +1136,7 @@ def main():
                         z = gram.analysis(audio.unsqueeze(1), rowpeak=peaks)
                     ea = eb = side_a.record_event()
             consumed[buf] = (ea, eb)
-            last["z"], last["loss"] = z, loss
+            last["audio"], last["z"], last["loss"] = audio, z, loss
 
         # control passes run `depth` steps ahead of their render
         # (two steps of lead, legal with three workspaces, measured slower: 0.232 vs 0.211 ms -- the capture order of the
@@ -1127,16 +1193,10 @@ def main():
         main.wait_stream(side_d)
         warmed["done"] = k >= nbuf
 
-    def sync_all():
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-            torch.cuda.synchronize()
-
     pipelined = not args.no_pipeline
     # ---- warm-up (eager), optional hipGraph capture of the K-step schedule
     run_steps(max(args.warmup, 2), pipelined)
-    torch.cuda.synchronize()
+    settle_before_capture(dev)      # N > 1: the RCCL watchdog must have nothing left to poll during the capture
     launch = "eager"
     graph = None
     if not args.no_graph:
@@ -1152,37 +1212,57 @@ def main():
             graph = None
             torch.cuda.synchronize()
 
-    # ---- timed regions: each one is EXACTLY K steps between barrier+synchronize brackets; R of them are timed
-    # one after the other (a single 5 ms region is dominated by pipeline fill/drain and clock ramp) and the MEDIAN
-    # region gives `value` / `ms_per_step`; the fastest one is reported next to it.
+    # ---- timed regions: each one is EXACTLY K steps between barrier+synchronize brackets.  A plain run times one; with
+    # --full R of them are timed one after the other (a single 5 ms region is dominated by pipeline fill/drain and clock
+    # ramp) and the MEDIAN region gives `value` / `ms_per_step`; the fastest one is reported next to it.
     def one_region():
-        sync_all()
-        t0 = time.perf_counter()
         if graph is not None:
             graph.replay()
         else:
             run_steps(args.steps, pipelined)
-        sync_all()
-        el = time.perf_counter() - t0
-        if world > 1:
-            t = torch.tensor([el], dtype=torch.float64, device=COLL_DEV)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            el = t.item()
-        return el
 
-    first = one_region()
-    replays = args.replays if args.replays > 0 else max(20, min(2000, int(0.25 / max(first, 1e-6)) + 1))
-    if world > 1:   # every rank must time the same number of regions
-        r = torch.tensor([replays], dtype=torch.int64, device=COLL_DEV)
-        dist.broadcast(r, 0)
-        replays = int(r.item())
-    regions = sorted(one_region() for _ in range(replays))
+    regions = timed_regions(one_region, args, world, dev)
+    replays = len(regions)
     elapsed = regions[len(regions) // 2]
     elapsed_min = regions[0]
     # the look-back chains of every render in the timed regions completed (a non-zero status word = NaN audio)
     for w_ in workspaces:
         assert voice.chain_status(w_) == 0, "voice render: a tile's bounded wait expired during the benchmark"
     loss_value = last["loss"].item()
+    ms_per_step = elapsed / args.steps * 1e3
+    value = world * B * SECONDS * args.steps / elapsed
+    result = {
+        "metric": "audio-seconds rendered+lossed/sec (whole node), batch=128 4s@44.1kHz",
+        "value": round(value, 1),
+        "unit": "audio-s/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "ms_per_step_min": round(elapsed_min / args.steps * 1e3, 4),
+        "timed_regions": replays, "timed_region_s": round(elapsed, 5), "timed_total_s": round(sum(regions), 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": "BASELINE configs[1]: torchsynth-style Voice render + PQMF(3) analysis + mel-L1 loss, "
+                        f"batch {B} x {SECONDS:g} s @ {SAMPLE_RATE} Hz per GPU",
+            "batch_per_gpu": B, "samples_per_voice": T, "launch": launch, "streams": 5, "pipelined": pipelined, "loss": loss_value,
+        },
+    }
+    # the last timed step's outputs: its audio buffer (before the row normalisation the two consumers apply on load), the
+    # PQMF(3) sub-bands and the mel-L1 loss
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"audio": last["audio"], "pqmf": last["z"], "loss": last["loss"]})
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- dominant-kernel timing with HIP events on the launch stream (eager: events cannot be read back
     # from inside a replayed graph).  Two passes over the same K steps:
@@ -1295,9 +1375,6 @@ def main():
     torch.cuda.synchronize()
     osc_ms_avg = e0.elapsed_time(e1) / args.steps
 
-    ms_per_step = elapsed / args.steps * 1e3
-    value = world * B * SECONDS * args.steps / elapsed
-
     # ---- the three audio-rate kernels of the step, each alone (isolated) and inside the pipelined schedule (in-step):
     # algorithmic HBM bytes per sample: render 8 (noise in + audio out), PQMF 8 (in + out),
     # mel-L1 against a cached target 4 + 4 * n_mels / hop = 5
@@ -1409,27 +1486,7 @@ def main():
                                                                  else " on v_mfma_f32_16x16x4_f32)"),
              "stft": knames["stft"].split("<")[0] + " (framed radix-8 FFT + power + mel projection + L1 against the cached target)"}
 
-    result = {
-        "metric": "audio-seconds rendered+lossed/sec (whole node), batch=128 4s@44.1kHz",
-        "value": round(value, 1),
-        "unit": "audio-s/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "ms_per_step_min": round(elapsed_min / args.steps * 1e3, 4),
-        "timed_regions": replays, "timed_region_s": round(elapsed, 5), "timed_total_s": round(sum(regions), 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": "BASELINE configs[1]: torchsynth-style Voice render + PQMF(3) analysis + mel-L1 loss, "
-                        f"batch {B} x {SECONDS:g} s @ {SAMPLE_RATE} Hz per GPU",
-            "batch_per_gpu": B, "samples_per_voice": T, "launch": launch, "streams": 5, "pipelined": pipelined, "loss": loss_value,
-        },
-        "roofline": {
+    result["roofline"] = {
             "kernel": kdesc[dom],
             "dominant_by": "largest in-step duration per step of the timed (pipelined) schedule",
             "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1462,7 +1519,6 @@ def main():
             "control_pass_in_step_us": None if not instep_ms.get("control") else round(instep_ms["control"] * 1e3, 1),
             "chain_frac_note": "22 B/sample (SURVEY.md 8d: render 8 + PQMF 8 + mel-L1 5, rounded up) x B x T / ms_per_step "
                                "/ 8 TB/s: the whole step against the HBM roofline (north_star target 0.70)",
-        },
     }
     # ---- driver-timed secondary legs (N = 1 only, after the headline's timed regions, never inside them): the MFMA
     # Gram of configs[2] / [3]'s loss and the configs[4] gradient step, a few hundred ms each

@@ -10,9 +10,11 @@ pretrain.py:98): every rank renders its own batch, gradients are averaged.  Here
                           point-to-point (7 links x ~153 GB/s per GPU) and ring collectives are per-link
                           bound, so buckets are few and large (default 128 MiB) rather than NVSwitch-sized.
   * ``all_reduce_mean``   the ``sync_dist=True`` metric reduction of vicreg_audio_params.py:117-120.
+  * ``settle_before_capture``  what a hipGraph capture of a step with RCCL collectives waits for before it begins.
 The embedding gather of vicreg.py:79-95 is ``vicreg.FullGatherLayer``.
 """
 import os
+import time
 
 import torch
 import torch.distributed as dist
@@ -43,6 +45,23 @@ def init_from_env(backend=None):
 
 def world_size():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
+# ProcessGroupNCCL's watchdog thread keeps the collectives issued outside a capture in a list and polls their end events
+# (hipEventQuery), retiring the completed ones, once per pass (every 100 ms).  A poll from that thread while another thread
+# captures a hipGraph can fail on ROCm even in capture mode "thread_local", and the watchdog turns the error into a process
+# abort (seen: an abort on a non-Python thread in the middle of capturing a training step with its bucket all-reduces).
+# Collectives issued during a capture are not put on that list, so a capture that begins after every earlier collective
+# has completed and has been retired leaves the watchdog nothing to poll.
+WATCHDOG_RETIRE_S = 0.3     # three watchdog passes
+
+
+def settle_before_capture(device=None):
+    """Wait until a hipGraph capture cannot race ProcessGroupNCCL's watchdog: the device idle and, with an RCCL process
+    group, the watchdog given WATCHDOG_RETIRE_S to retire the completed collectives it tracks."""
+    torch.cuda.synchronize(device)
+    if dist.is_available() and dist.is_initialized() and dist.get_backend() == "nccl":
+        time.sleep(WATCHDOG_RETIRE_S)
 
 
 def all_reduce_mean(t):

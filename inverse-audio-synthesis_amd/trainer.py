@@ -217,7 +217,7 @@ class Trainer:
                 self._graph_warm = n + 1
                 one_step()
                 return
-            torch.cuda.synchronize(self.device)
+            ias_dist.settle_before_capture(self.device)   # (the RCCL watchdog must have nothing left to poll)
             g = torch.cuda.CUDAGraph()
             try:
                 # with collectives in the step the capture must not trip over RCCL's watchdog thread polling its events

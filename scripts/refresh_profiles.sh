@@ -15,11 +15,11 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 step() { echo "[refresh_profiles] $*" >> $O/progress.log; echo "[refresh_profiles] $*"; }
 
-step bench default; python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
-step bench nopipeline; python3 $R/bench.py --no-pipeline --no-cpu-baseline > $O/bench_nopipeline.json 2> $O/bench_nopipeline.err
-step bench vicreg; python3 $R/bench.py --workload vicreg > $O/bench_vicreg128.json 2> $O/bench_vicreg128.err
-python3 $R/bench.py --workload vicreg --batch 1024 --no-cpu-baseline > $O/bench_vicreg1024.json 2> $O/bench_vicreg1024.err
-step bench gradstep; python3 $R/bench.py --workload gradstep --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_gradstep.json 2> $O/bench_gradstep.err
+step bench default; python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+step bench nopipeline; python3 $R/bench.py --full --no-pipeline --no-cpu-baseline > $O/bench_nopipeline.json 2> $O/bench_nopipeline.err
+step bench vicreg; python3 $R/bench.py --full --workload vicreg > $O/bench_vicreg128.json 2> $O/bench_vicreg128.err
+python3 $R/bench.py --full --workload vicreg --batch 1024 --no-cpu-baseline > $O/bench_vicreg1024.json 2> $O/bench_vicreg1024.err
+step bench gradstep; python3 $R/bench.py --full --workload gradstep --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_gradstep.json 2> $O/bench_gradstep.err
 
 kst() { # name, bench args...
   local name=$1; shift
@@ -28,11 +28,11 @@ kst() { # name, bench args...
   f=$(find $O/prof_$name -name out_kernel_stats.csv | head -1); [ -n "$f" ] && cp $f $O/kstats_$name.csv
   rm -rf $O/prof_$name          # the raw kernel trace is tens of MB; gpurun merges at most 64 MiB back
 }
-kst default --no-cpu-baseline --no-legs
-kst nopipeline --no-pipeline --no-graph --no-cpu-baseline
-kst vicreg128 --workload vicreg --no-cpu-baseline --no-graph --steps 20 --warmup 3
-kst vicreg1024 --workload vicreg --batch 1024 --no-cpu-baseline --no-graph --steps 20 --warmup 3
-kst gradstep --workload gradstep --steps 5 --warmup 2 --no-cpu-baseline --no-graph
+kst default --full --no-cpu-baseline --no-legs
+kst nopipeline --full --no-pipeline --no-graph --no-cpu-baseline
+kst vicreg128 --full --workload vicreg --no-cpu-baseline --no-graph --steps 20 --warmup 3
+kst vicreg1024 --full --workload vicreg --batch 1024 --no-cpu-baseline --no-graph --steps 20 --warmup 3
+kst gradstep --full --workload gradstep --steps 5 --warmup 2 --no-cpu-baseline --no-graph
 
 step pmc traffic
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch -o out --output-format csv -- python3 $R/scripts/diag/time_stages.py > $O/pmc_fetch.log 2>&1

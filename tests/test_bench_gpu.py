@@ -27,7 +27,7 @@ def _run_bench(extra, timeout=900, legs=False, torchrun=False):
         head = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", str(port), os.path.join(ROOT, "bench.py")]
     r = subprocess.run(head + ["--gpus", "2", "--steps", "5", "--warmup", "2",
-                               "--no-cpu-baseline", "--replays", "5"] + ([] if legs else ["--no-legs"]) + extra, env=env,
+                               "--no-cpu-baseline", "--replays", "5"] + (["--full"] if legs else ["--no-legs"]) + extra, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -36,7 +36,7 @@ def _run_bench(extra, timeout=900, legs=False, torchrun=False):
 
 
 def test_bench_synth_two_ranks(lib, dev):
-    j = _run_bench([])
+    j = _run_bench(["--full"])
     assert j["n_gpus"] == 2 and j["steps"] == 5 and j["scaling"] == "weak" and j["unit"] == "audio-s/s"
     B = j["config"]["batch_per_gpu"]
     assert B == 128
@@ -92,3 +92,31 @@ def test_bench_two_ranks_run_the_collective_legs(lib, dev):
     assert "error" not in gs, gs
     assert gs["global_batch"] == 128 and gs["n_gpus"] == 2 and gs["ms_per_step"] > 0
     assert abs(gs["value"] - 2 * 64 * 4.0 / (gs["ms_per_step"] * 1e-3)) <= 1e-3 * gs["value"]
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_outputs(lib, dev, tmp_path):
+    """The plain command on one GPU: exactly K timed steps (one region), the headline fields and nothing that needs runs
+    of its own; --dump-outputs writes the last timed step's audio, PQMF sub-bands and loss within 64 MB."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                        "--dump-outputs", str(out)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["steps"] == 4 and j["timed_regions"] == 1 and j["n_gpus"] == 1
+    assert j["unit"] == "audio-s/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert abs(j["value"] - 128 * 4.0 / (j["ms_per_step"] * 1e-3)) <= 1e-3 * j["value"]
+    assert not {"roofline", "legs", "cpu_baseline"} & set(j)
+    files = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert set(files) == {"audio", "pqmf", "loss"}
+    assert all(a.dtype == np.float32 for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 * 10**6
+    T = 176400
+    assert files["audio"].shape[1:] == (T,) and files["pqmf"].shape[1:] == (3, T // 3)
+    assert files["audio"].shape[0] == files["pqmf"].shape[0] >= 1
+    assert np.isfinite(files["audio"]).all() and np.isfinite(files["pqmf"]).all()
+    assert float(files["loss"]) == pytest.approx(j["config"]["loss"], rel=1e-6)

@@ -215,6 +215,8 @@ def test_gathered_loss_step_captures_with_its_rccl_collectives(lib, dev, nccl_gr
     step(); step()
     torch.cuda.synchronize()
     eager = ([float(o) for o in state["out"]], state["g"][0].clone(), state["g"][1].clone())
+    from inverse_audio_synthesis_amd.dist import settle_before_capture
+    settle_before_capture(dev)              # as the Trainer does: the RCCL watchdog must have nothing left to poll
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph, capture_error_mode="thread_local"):
         for _ in range(K):
