@@ -310,6 +310,29 @@ long long ias_l1_partials_count(long long n);
 int ias_l1_partials(const float* x, const float* y, long long n, double* partials, void* stream);
 int ias_l1_grad(const float* x, const float* y, const float* g_loss, float scale, long long n, float* gx, void* stream);
 
+/* ---- Sound matching (inverse-audio-synthesis_amd/match.py).
+ * Per-row L1: out[b] (device fp32) = sum_i |values[b,i] - target[b,i]| / n over rows of n floats (values, target [B,n]
+ * fp32; what ias_stft wrote for the audio and the target).  partials [B][ias_l1_rows_partials_count(n)] doubles: scratch
+ * (one per 4096-float chunk of a row, folded in chunk order).  A row's result does not depend on its position in the
+ * batch or on the other rows (same bits).
+ * ias_stft_loss_backward_rows: d (sum_b g_rows[b] * scale * sum_row |V - target|) / d audio, g_rows [B] device fp32;
+ * the other arguments as ias_stft_loss_backward (loss_mode 1).  Rows with g_rows[b] == 0 get exactly 0.
+ * ias_match_adam_step: one Adam step per row of params [B,P] (P <= 128; grad, m, v, best_params [B,P] fp32; step,
+ * skipped [B] int32; loss [B] fp32 = the loss of params as they are; best_loss [B] fp64; free_cols [P], active [B]
+ * uint8).  For each active row: loss < best_loss -> best_params = params, best_loss = loss; then, if the loss or a free
+ * column's gradient is not finite, skipped += 1 and nothing else changes; otherwise step += 1 and torch.optim.Adam's
+ * update (bias corrections of that row's step) on the free columns, clamped to [0, 1].  Frozen columns and inactive rows
+ * are left as they are. */
+int ias_l1_rows_partials_count(long long n);
+int ias_l1_rows(const float* values, const float* target, int B, long long n, double* partials, float* out, void* stream);
+int ias_stft_loss_backward_rows(const float* audio, const float* window, const float* tables, const int* mel_start,
+                                const int* mel_count, const int* mel_woff, const float* mel_w, int mel_nnz,
+                                const float* target, const float* g_rows, float* frame_grad, float* g_audio, int B, int T,
+                                int n_fft, int hop, int n_out, int power, float scale, void* stream);
+int ias_match_adam_step(float* params, const float* grad, float* m, float* v, int* step, const float* loss,
+                        double* best_loss, float* best_params, const unsigned char* free_cols, const unsigned char* active,
+                        int* skipped, int B, int P, float lr, float beta1, float beta2, float eps, void* stream);
+
 /* sums[3] (doubles) = column sums of partials [n][3], fixed order (deterministic); when mean_out is not
  * NULL also mean_out[0] = (float)(sums[0] * scale). */
 int ias_reduce_partials(const double* partials, long long n, double* sums, double scale, float* mean_out,

@@ -1,0 +1,166 @@
+// Sound matching (MI355X / gfx950): the per-sound L1 of two spectrogram tensors and the per-sound Adam update of the
+// matcher (inverse-audio-synthesis_amd/match.py).
+//
+// The reference's inverse loop -- params -> synth -> mel-L1 against the true audio -- is the commented-out block
+// /root/reference/audio_to_params.py:56-172; its notebook wants one candidate and one distance per test sound
+// (/root/reference/evaluate_audio_representations.py:202-231).  Fitting each sound on its own needs a loss per sound
+// (a batch mean couples every sound's gradient to the batch size) and an optimizer whose state is per row.
+//
+// l1_rows_partials_kernel: grid (nchunks, B); workgroup (c, b) sums |v - t| over elements [c L1R_CHUNK, (c + 1) L1R_CHUNK)
+//   of row b.  Thread t takes elements chunk + (k L1R_THREADS + t) * 4 + e, k < L1R_ITERS, e < 4, and adds them one by
+//   one in that order whether it loads them as float4 or as floats (a row's 16-byte alignment depends on its position in
+//   the batch when the row length is not a multiple of 4: the order of additions must not).  The 256 fp32 sums are
+//   folded in fp64 in a fixed butterfly.  Nothing depends on b but the row pointer: a row's partials are the same bits
+//   wherever it sits in the batch.
+// l1_rows_fold_kernel: one lane per row adds the row's partials in chunk order and divides by the row length (fp64).
+// match_adam_kernel: one 64-lane workgroup per row; see ias_match_adam_step below.
+#include "ias_common.h"
+#include <cstdint>
+
+#define L1R_THREADS 256
+#define L1R_ITERS 4
+#define L1R_CHUNK (L1R_THREADS * 4 * L1R_ITERS)      // 4096 floats per workgroup
+
+__global__ __launch_bounds__(L1R_THREADS) void l1_rows_partials_kernel(const float* __restrict__ v,
+                                                                       const float* __restrict__ t, long long n,
+                                                                       int nchunks, double* __restrict__ partials) {
+  __shared__ double s_red[L1R_THREADS / 64];
+  const int c = blockIdx.x, b = blockIdx.y;
+  const float* vr = v + (size_t)b * n;
+  const float* tr = t + (size_t)b * n;
+  const long long base = (long long)c * L1R_CHUNK;
+  const bool vec = ((reinterpret_cast<uintptr_t>(vr) | reinterpret_cast<uintptr_t>(tr)) & 15) == 0;
+  float acc = 0.0f;
+#pragma unroll
+  for (int it = 0; it < L1R_ITERS; ++it) {
+    const long long i = base + ((long long)it * L1R_THREADS + threadIdx.x) * 4;
+    if (vec && i + 3 < n) {
+      const float4 a = *reinterpret_cast<const float4*>(vr + i), q = *reinterpret_cast<const float4*>(tr + i);
+      acc += fabsf(a.x - q.x);
+      acc += fabsf(a.y - q.y);
+      acc += fabsf(a.z - q.z);
+      acc += fabsf(a.w - q.w);
+    } else {
+      for (int e = 0; e < 4; ++e)
+        if (i + e < n) acc += fabsf(vr[i + e] - tr[i + e]);
+    }
+  }
+  double s = (double)acc;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double r = s_red[0];
+    for (int w = 1; w < L1R_THREADS / 64; ++w) r += s_red[w];
+    partials[(size_t)b * nchunks + c] = r;
+  }
+}
+
+__global__ __launch_bounds__(256) void l1_rows_fold_kernel(const double* __restrict__ partials, int B, int nchunks,
+                                                          double count, float* __restrict__ out) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const double* p = partials + (size_t)b * nchunks;
+  double s = p[0];
+  for (int c = 1; c < nchunks; ++c) s += p[c];
+  out[b] = (float)(s / count);
+}
+
+// ------------------------------------------------------------------------------------------------ per-row Adam
+// torch.optim.Adam's step (no weight decay, no amsgrad) with a step counter per row, the best-so-far bookkeeping of the
+// matcher and a row skip on non-finite input.  Lane k owns columns k and k + 64 (P <= 128) from the load to the store,
+// so the copy to best_params reads the parameters before this update writes them.
+#define ADAM_THREADS 64
+#define ADAM_MAX_P (2 * ADAM_THREADS)
+
+__global__ __launch_bounds__(ADAM_THREADS) void match_adam_kernel(float* __restrict__ params, const float* __restrict__ grad,
+                                                                  float* __restrict__ m, float* __restrict__ v,
+                                                                  int* __restrict__ step, const float* __restrict__ loss,
+                                                                  double* __restrict__ best_loss,
+                                                                  float* __restrict__ best_params,
+                                                                  const unsigned char* __restrict__ free_cols,
+                                                                  const unsigned char* __restrict__ active,
+                                                                  int* __restrict__ skipped, int P, float lr, float beta1,
+                                                                  float beta2, float eps) {
+  const int b = blockIdx.x, k = threadIdx.x;
+  if (!active[b]) return;                              // uniform over the workgroup
+  const size_t row = (size_t)b * P;
+  const float lb = loss[b];
+  const double best = best_loss[b];
+  const int t_prev = step[b];
+  bool bad = !isfinite(lb);
+  float p[2], g[2];
+  bool fr[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int c = k + u * ADAM_THREADS;
+    fr[u] = c < P && free_cols[c] != 0;
+    p[u] = c < P ? params[row + c] : 0.0f;
+    g[u] = fr[u] ? grad[row + c] : 0.0f;
+    if (fr[u] && !isfinite(g[u])) bad = true;
+  }
+  // every lane has read best_loss / step before lane 0 writes them
+  const bool skip = __syncthreads_or(bad) != 0;
+  if ((double)lb < best) {                             // strict: a tie keeps the earlier parameters
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int c = k + u * ADAM_THREADS;
+      if (c < P) best_params[row + c] = p[u];
+    }
+    if (k == 0) best_loss[b] = (double)lb;
+  }
+  if (skip) {
+    if (k == 0) skipped[b] += 1;
+    return;
+  }
+  const int t = t_prev + 1;
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)t));
+  const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)t));
+  const float step_size = lr / bc1;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    if (!fr[u]) continue;
+    const size_t i = row + k + u * ADAM_THREADS;
+    const float mi = m[i] + (1.0f - beta1) * (g[u] - m[i]);        // exp_avg.lerp_(grad, 1 - beta1)
+    const float vi = v[i] * beta2 + (1.0f - beta2) * g[u] * g[u];  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    const float pn = p[u] - step_size * (mi / denom);
+    m[i] = mi;
+    v[i] = vi;
+    params[i] = fminf(fmaxf(pn, 0.0f), 1.0f);
+  }
+  if (k == 0) step[b] = t;
+}
+
+// ------------------------------------------------------------------------------------------------ C ABI
+extern "C" int ias_l1_rows_partials_count(long long n) {
+  if (n <= 0 || (n + L1R_CHUNK - 1) / L1R_CHUNK > 2147483647LL) return IAS_ERR_ARG;
+  return (int)((n + L1R_CHUNK - 1) / L1R_CHUNK);
+}
+
+extern "C" int ias_l1_rows(const float* values, const float* target, int B, long long n, double* partials, float* out,
+                           void* stream_) {
+  if (!values || !target || !partials || !out || B <= 0 || B > 65535 || n <= 0) return IAS_ERR_ARG;
+  const int nchunks = ias_l1_rows_partials_count(n);
+  if (nchunks <= 0) return IAS_ERR_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  hipLaunchKernelGGL(l1_rows_partials_kernel, dim3(nchunks, B), dim3(L1R_THREADS), 0, stream, values, target, n, nchunks,
+                     partials);
+  hipLaunchKernelGGL(l1_rows_fold_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, partials, B, nchunks, (double)n, out);
+  return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
+}
+
+extern "C" int ias_match_adam_step(float* params, const float* grad, float* m, float* v, int* step, const float* loss,
+                                   double* best_loss, float* best_params, const unsigned char* free_cols,
+                                   const unsigned char* active, int* skipped, int B, int P, float lr, float beta1,
+                                   float beta2, float eps, void* stream_) {
+  if (!params || !grad || !m || !v || !step || !loss || !best_loss || !best_params || !free_cols || !active || !skipped)
+    return IAS_ERR_ARG;
+  if (B <= 0 || P <= 0 || P > ADAM_MAX_P) return IAS_ERR_ARG;
+  if (!(lr >= 0.0f) || !(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f) || !(eps > 0.0f))
+    return IAS_ERR_ARG;
+  hipLaunchKernelGGL(match_adam_kernel, dim3(B), dim3(ADAM_THREADS), 0, (hipStream_t)stream_, params, grad, m, v, step, loss,
+                     best_loss, best_params, free_cols, active, skipped, P, lr, beta1, beta2, eps);
+  return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
+}

@@ -232,7 +232,9 @@ __global__ __launch_bounds__(SG_THREADS) void stft_grad_frames_kernel(SgArgs g) 
 }
 
 // g_audio[b,j] = g_loss * sum over the padded positions q that read audio[j] (itself and its reflections) of the
-// frames covering q.
+// frames covering q.  ROWS: the cotangent is the device vector g_loss[B] (the per-sound losses, ias_stft_loss_backward_rows),
+// and a row whose g_loss[b] is 0 gets exactly 0.
+template <bool ROWS>
 __global__ __launch_bounds__(SG_THREADS) void stft_grad_ola_kernel(const float* __restrict__ frame_grad,
                                                                    const float* __restrict__ g_loss,
                                                                    float* __restrict__ g_audio, int T, int F, int N,
@@ -254,11 +256,18 @@ __global__ __launch_bounds__(SG_THREADS) void stft_grad_ola_kernel(const float* 
     int f_lo = q - N + 1 <= 0 ? 0 : (q - N + 1 + hop - 1) / hop;
     for (int f = f_lo; f <= f_hi; ++f) acc += fg[(size_t)f * N + (q - f * hop)];
   }
-  g_audio[(size_t)b * T + j] = g_loss ? acc * g_loss[0] : acc;
+  if constexpr (ROWS) {
+    const float g = g_loss[b];
+    g_audio[(size_t)b * T + j] = g == 0.0f ? 0.0f : acc * g;
+  } else {
+    g_audio[(size_t)b * T + j] = g_loss ? acc * g_loss[0] : acc;
+  }
 }
 
 // The same from chunk spans (ias_stft_grad_spans): span c of row b covers the padded samples [c G hop, c G hop + L) with
-// the sum over ITS frames; a sample lies in at most two spans (G hop >= N - hop), added lower chunk first.
+// the sum over ITS frames; a sample lies in at most two spans (G hop >= N - hop), added lower chunk first.  ROWS: as in
+// stft_grad_ola_kernel.
+template <bool ROWS>
 __global__ __launch_bounds__(SG_THREADS) void stft_grad_combine_kernel(const float* __restrict__ spans,
                                                                        const float* __restrict__ g_loss,
                                                                        float* __restrict__ g_audio, int T, int F, int N,
@@ -283,7 +292,12 @@ __global__ __launch_bounds__(SG_THREADS) void stft_grad_combine_kernel(const flo
     if (q - c * gh < (nf - 1) * hop + N) v += sp[(size_t)c * L + (q - c * gh)];
     acc += v;
   }
-  g_audio[(size_t)b * T + j] = g_loss ? acc * g_loss[0] : acc;
+  if constexpr (ROWS) {
+    const float g = g_loss[b];
+    g_audio[(size_t)b * T + j] = g == 0.0f ? 0.0f : acc * g;
+  } else {
+    g_audio[(size_t)b * T + j] = g_loss ? acc * g_loss[0] : acc;
+  }
 }
 
 // Several resolutions at once (MR-STFT): g_audio = g_loss * sum over the resolutions, in their order, of the above --
@@ -401,11 +415,12 @@ extern "C" int ias_stft_grad_spans(const float* audio, const float* tables, cons
                                    const double* coef, float* chunk_spans, int B, int T, int n_fft, int hop, int power,
                                    int loss_mode, float scale, float eps, int* plan_host, void* stream);
 
-extern "C" int ias_stft_loss_backward(const float* audio, const float* window, const float* tables, const int* mel_start,
-                                      const int* mel_count, const int* mel_woff, const float* mel_w, int mel_nnz,
-                                      const float* target, const float* g_loss, const double* coef, float* frame_grad,
-                                      float* g_audio, int B, int T, int n_fft, int hop, int n_out, int power,
-                                      int loss_mode, float scale, float eps, void* stream_) {
+template <bool ROWS>
+static int stft_loss_backward(const float* audio, const float* window, const float* tables, const int* mel_start,
+                              const int* mel_count, const int* mel_woff, const float* mel_w, int mel_nnz,
+                              const float* target, const float* g_loss, const double* coef, float* frame_grad,
+                              float* g_audio, int B, int T, int n_fft, int hop, int n_out, int power, int loss_mode,
+                              float scale, float eps, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!audio || !window || !target || !frame_grad || !g_audio || B <= 0 || B > 65535 || hop <= 0) return IAS_ERR_ARG;
   if (n_fft != 512 && n_fft != 1024 && n_fft != 2048) return IAS_ERR_UNSUPPORTED;
@@ -429,7 +444,7 @@ extern "C" int ias_stft_loss_backward(const float* audio, const float* window, c
                                          target, coef, frame_grad, B, T, n_fft, hop, power, loss_mode, scale, eps, plan,
                                          stream_);
       if (rs == IAS_OK) {
-        hipLaunchKernelGGL(stft_grad_combine_kernel, dim3((T + SG_THREADS - 1) / SG_THREADS, B), dim3(SG_THREADS), 0,
+        hipLaunchKernelGGL(stft_grad_combine_kernel<ROWS>, dim3((T + SG_THREADS - 1) / SG_THREADS, B), dim3(SG_THREADS), 0,
                            stream, frame_grad, g_loss, g_audio, T, F, n_fft, hop, plan[0], plan[1], plan[2]);
         return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
       }
@@ -438,7 +453,7 @@ extern "C" int ias_stft_loss_backward(const float* audio, const float* window, c
     const int rc = ias_stft_grad_frames(audio, tables, mel_start, mel_count, mel_woff, mel_w, mel ? mel_nnz : 0, n_out,
                                         target, coef, frame_grad, B, T, n_fft, hop, power, loss_mode, scale, eps, stream_);
     if (rc != IAS_OK) return rc;
-    hipLaunchKernelGGL(stft_grad_ola_kernel, dim3((T + SG_THREADS - 1) / SG_THREADS, B), dim3(SG_THREADS), 0, stream,
+    hipLaunchKernelGGL(stft_grad_ola_kernel<ROWS>, dim3((T + SG_THREADS - 1) / SG_THREADS, B), dim3(SG_THREADS), 0, stream,
                        frame_grad, g_loss, g_audio, T, F, n_fft, hop);
     return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
   }
@@ -458,9 +473,31 @@ extern "C" int ias_stft_loss_backward(const float* audio, const float* window, c
   const int pairs = (F + 1) / 2;
   hipLaunchKernelGGL(stft_grad_frames_kernel, dim3((pairs + SG_PAIRS - 1) / SG_PAIRS, B), dim3(SG_THREADS), lds, stream,
                      g);
-  hipLaunchKernelGGL(stft_grad_ola_kernel, dim3((T + SG_THREADS - 1) / SG_THREADS, B), dim3(SG_THREADS), 0, stream,
+  hipLaunchKernelGGL(stft_grad_ola_kernel<ROWS>, dim3((T + SG_THREADS - 1) / SG_THREADS, B), dim3(SG_THREADS), 0, stream,
                      frame_grad, g_loss, g_audio, T, F, n_fft, hop);
   return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
+}
+
+extern "C" int ias_stft_loss_backward(const float* audio, const float* window, const float* tables, const int* mel_start,
+                                      const int* mel_count, const int* mel_woff, const float* mel_w, int mel_nnz,
+                                      const float* target, const float* g_loss, const double* coef, float* frame_grad,
+                                      float* g_audio, int B, int T, int n_fft, int hop, int n_out, int power,
+                                      int loss_mode, float scale, float eps, void* stream_) {
+  return stft_loss_backward<false>(audio, window, tables, mel_start, mel_count, mel_woff, mel_w, mel_nnz, target, g_loss,
+                                   coef, frame_grad, g_audio, B, T, n_fft, hop, n_out, power, loss_mode, scale, eps, stream_);
+}
+
+// d (sum_b g_rows[b] L_b) / d audio for the per-sound L1 losses L_b = scale * sum over row b of |V - target| (scale
+// = 1 / (F n_out): the row means).  L1 is linear in its cotangent: the same frame / span kernels as
+// ias_stft_loss_backward(loss_mode 1), with the combine reading g_rows[b] instead of one scalar.
+extern "C" int ias_stft_loss_backward_rows(const float* audio, const float* window, const float* tables,
+                                           const int* mel_start, const int* mel_count, const int* mel_woff,
+                                           const float* mel_w, int mel_nnz, const float* target, const float* g_rows,
+                                           float* frame_grad, float* g_audio, int B, int T, int n_fft, int hop, int n_out,
+                                           int power, float scale, void* stream_) {
+  if (!g_rows) return IAS_ERR_ARG;
+  return stft_loss_backward<true>(audio, window, tables, mel_start, mel_count, mel_woff, mel_w, mel_nnz, target, g_rows,
+                                  nullptr, frame_grad, g_audio, B, T, n_fft, hop, n_out, power, 1, scale, 0.0f, stream_);
 }
 
 // ------------------------------------------------------------------------------------------------ scalar glue

@@ -168,6 +168,28 @@ class AudioToParams(nn.Module):
     def test_step(self, batch, batch_idx=None):
         return self._step(batch, batch_idx, "test")
 
+    @torch.no_grad()
+    def predict(self, audio):
+        """audio [N, T] -> predicted params01 [N, 78]: the frozen VICReg audio backbone and the MLP, both in eval mode
+        (dropout off, BatchNorm on its running statistics); the module's training mode is restored afterwards."""
+        was_training = self.training
+        self.eval()
+        try:
+            repr_ = self.vicreg.vicreg.backbone_audio(audio.unsqueeze(1))
+            return self.audio_repr_to_params(repr_).float()
+        finally:
+            self.train(was_training)
+
+    def match(self, audio, steps=200, **kw):
+        """Sound matching (match.SoundMatcher) started from the MLP's prediction: audio [N, T] at this module's voice
+        rate and length -> match.MatchResult.  ``kw``: SoundMatcher's arguments (loss, lr, betas, eps, frozen; the mel
+        settings default to cfg.mel) and ``return_audio``."""
+        from .match import SoundMatcher
+        return_audio = kw.pop("return_audio", False)
+        kw.setdefault("mel_kwargs", dict(self.cfg.mel))
+        matcher = SoundMatcher(self.voice, **kw)
+        return matcher.fit(audio, init_params01=self.predict(audio), steps=steps, return_audio=return_audio)
+
     def configure_optimizers(self):
         a = self.cfg.audio_to_params
         params = [p for p in self.parameters() if p.requires_grad]

@@ -1,0 +1,144 @@
+"""Sound matching: fit the 78 Voice parameters to given audio, each sound on its own.
+
+This closes the loop the reference left commented out (/root/reference/audio_to_params.py:56-172: params -> synth ->
+mel-L1 against the true audio) as a product feature, and returns what its notebook wanted in the end
+(/root/reference/evaluate_audio_representations.py:202-231): a candidate and a distance per target sound.
+
+Per chunk of ``voice.batch_size`` targets, every iteration is
+
+    audio = voice.render(p)                      HIP render with its adjoint (voice_grad.py), normalize=True
+    L     = loss.per_item(audio, target)         [B] per-sound spectral L1 (spectral.py, csrc/match_kernels.hip)
+    L.backward(active)                           per-row cotangent (ias_stft_loss_backward_rows): a sound's gradient
+                                                 does not depend on the batch, padded rows get exactly 0
+    ias_match_adam_step                          best-so-far, non-finite skip, Adam per row, clamp to [0, 1]
+
+with all state on the device and no host read inside the loop.
+"""
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from . import _lib
+from . import voice_spec as S
+from .spectral import MelSpectrogramL1, STFTL1
+
+
+@dataclass
+class MatchResult:
+    params01: torch.Tensor          # [N, 78] best parameters per sound
+    loss: torch.Tensor              # [N] fp32: the loss of params01, exactly
+    initial_loss: torch.Tensor      # [N] fp32: the loss of the initial parameters
+    skipped: torch.Tensor           # [N] int32: iterations skipped for a non-finite loss or gradient
+    audio: Optional[torch.Tensor] = None   # [N, T] render of params01 (fit(return_audio=True))
+
+
+def match_adam_step(params01, grad, m, v, step, loss, best_loss, best_params, free, active, skipped, lr, betas, eps):
+    """One launch of ias_match_adam_step over [B, P] (see include/ias_hip.h).  Updates params01, m, v, step, best_loss,
+    best_params and skipped in place."""
+    B, P = params01.shape
+    for t, dt, shape in ((params01, torch.float32, (B, P)), (grad, torch.float32, (B, P)), (m, torch.float32, (B, P)),
+                         (v, torch.float32, (B, P)), (best_params, torch.float32, (B, P)), (step, torch.int32, (B,)),
+                         (loss, torch.float32, (B,)), (best_loss, torch.float64, (B,)), (free, torch.uint8, (P,)),
+                         (active, torch.uint8, (B,)), (skipped, torch.int32, (B,))):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"match_adam_step: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    st = _lib.load().ias_match_adam_step(
+        _lib.ptr(params01), _lib.ptr(grad), _lib.ptr(m), _lib.ptr(v), _lib.ptr(step), _lib.ptr(loss), _lib.ptr(best_loss),
+        _lib.ptr(best_params), _lib.ptr(free), _lib.ptr(active), _lib.ptr(skipped), B, P, float(lr), float(betas[0]),
+        float(betas[1]), float(eps), _lib.stream())
+    _lib.check(st, "ias_match_adam_step")
+
+
+class SoundMatcher:
+    """Fit Voice parameters to target sounds by descent through the HIP render and a per-sound spectral loss.
+
+    ``loss``: "mel_l1" (``MelSpectrogramL1(sample_rate=voice rate, **mel_kwargs)``) or "stft_l1" (``STFTL1(**stft_kwargs)``).
+    ``frozen``: keys as ``Voice.get_parameters()`` ((module, name) pairs) that keep their initial value.  The matcher
+    renders with explicit parameters: it leaves ``voice.params01`` and the voice's own frozen set alone."""
+
+    def __init__(self, voice, loss="mel_l1", mel_kwargs=None, stft_kwargs=None, lr=0.01, betas=(0.9, 0.999), eps=1e-8,
+                 frozen=()):
+        self.voice = voice
+        if loss == "mel_l1":
+            kw = dict(mel_kwargs or {})
+            kw.setdefault("sample_rate", voice.synthconfig.sample_rate)
+            self.loss = MelSpectrogramL1(**kw)
+        elif loss == "stft_l1":
+            self.loss = STFTL1(**dict(stft_kwargs or {}))
+        else:
+            raise ValueError(f"unknown matching loss {loss!r}: 'mel_l1' or 'stft_l1'")
+        self.loss_kind = loss
+        self.loss.to(voice.params01.device)
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        keys = [(m, n) for (m, n, *_r) in S.PARAMS]
+        frozen = [tuple(k) for k in frozen]
+        for k in frozen:
+            if k not in S.INDEX:
+                raise KeyError(f"unknown Voice parameter {k}")
+        self.free = torch.tensor([k not in frozen for k in keys], dtype=torch.uint8, device=voice.params01.device)
+
+    def _per_item(self, audio, target):
+        if self.loss_kind == "mel_l1":
+            return self.loss.per_item(audio, target_mel=target)
+        return self.loss.per_item(audio, target_values=target)
+
+    def fit(self, target_audio, init_params01=None, steps=200, return_audio=False):
+        """target_audio [N, T] (device, T == voice.synthconfig.buffer_size); init_params01 [N, 78] in 0..1 (None: 0.5)
+        -> ``MatchResult``.  Targets go through in chunks of ``voice.batch_size``; the last chunk is padded with inactive
+        rows (zero cotangent, never updated, not returned)."""
+        voice = self.voice
+        B, T = voice.batch_size, voice.synthconfig.buffer_size
+        dev = voice.params01.device
+        if target_audio.dim() != 2 or target_audio.shape[1] != T:
+            raise ValueError(f"target_audio must be [N, {T}] (the voice's buffer), got {tuple(target_audio.shape)}")
+        N = target_audio.shape[0]
+        if init_params01 is None:
+            init_params01 = torch.full((N, S.NPARAMS), 0.5, dtype=torch.float32, device=dev)
+        if tuple(init_params01.shape) != (N, S.NPARAMS):
+            raise ValueError(f"init_params01 must be [{N}, {S.NPARAMS}], got {tuple(init_params01.shape)}")
+        target_audio = target_audio.detach().to(device=dev, dtype=torch.float32)
+        init_params01 = init_params01.detach().to(device=dev, dtype=torch.float32).clamp(0.0, 1.0)
+        outs = [self._fit_chunk(target_audio[s:s + B], init_params01[s:s + B], int(steps), return_audio)
+                for s in range(0, N, B)]
+        cat = lambda i: torch.cat([o[i] for o in outs])     # noqa: E731
+        return MatchResult(params01=cat(0), loss=cat(1), initial_loss=cat(2), skipped=cat(3),
+                           audio=cat(4) if return_audio else None)
+
+    def _fit_chunk(self, target, init, steps, return_audio):
+        voice = self.voice
+        B, n = voice.batch_size, target.shape[0]
+        dev = target.device
+        active = torch.zeros(B, dtype=torch.uint8, device=dev)
+        active[:n] = 1
+        if n < B:                                    # padded rows: silence against centre parameters
+            target = torch.cat([target, target.new_zeros((B - n, target.shape[1]))])
+            init = torch.cat([init, init.new_full((B - n, S.NPARAMS), 0.5)])
+        cot = active.to(torch.float32)
+        with torch.no_grad():
+            tgt = self.loss.target(target)
+        p = init.clone().contiguous()
+        m, v = torch.zeros_like(p), torch.zeros_like(p)
+        step = torch.zeros(B, dtype=torch.int32, device=dev)
+        skipped = torch.zeros(B, dtype=torch.int32, device=dev)
+        best_loss = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
+        best_params = p.clone()
+        initial = None
+        for _ in range(steps):
+            q = p.clone().requires_grad_(True)
+            loss = self._per_item(voice.render(q, normalize=True), tgt)
+            if initial is None:
+                initial = loss.detach().clone()
+            loss.backward(cot)
+            match_adam_step(p, q.grad, m, v, step, loss.detach(), best_loss, best_params, self.free, active, skipped,
+                            self.lr, self.betas, self.eps)
+        with torch.no_grad():                        # the last parameters compete for "best" too
+            last = self._per_item(voice.render(p, normalize=True), tgt)
+            if initial is None:
+                initial = last.clone()
+            better = (active != 0) & (last.double() < best_loss)
+            best_params = torch.where(better.unsqueeze(1), p, best_params)
+            best_loss = torch.where(better, last.double(), best_loss)
+            audio = voice.render(best_params, normalize=True)[:n].clone() if return_audio else None
+        return best_params[:n], best_loss[:n].float(), initial[:n], skipped[:n], audio

@@ -36,3 +36,11 @@ def nearest(queries, bank, k=1):
     d = torch.cdist(queries, bank)
     dist, idx = torch.topk(d, k, dim=1, largest=False)
     return dist, idx
+
+
+@torch.no_grad()
+def init_from_bank(model, audio, bank_embs, bank_params):
+    """Starting point for sound matching (match.SoundMatcher.fit's ``init_params01``): the parameters [N, 78] of the
+    bank item nearest to each query sound audio [N, T] in embedding space."""
+    _dist, idx = nearest(embed_audio(model, audio), bank_embs, k=1)
+    return bank_params[idx[:, 0]].clone()

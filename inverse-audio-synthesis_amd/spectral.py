@@ -196,6 +196,23 @@ class STFTPlan(nn.Module):
         return sums if mean is None else mean
 
 
+    def l1_rows(self, values, target_values):
+        """Per-row mean |values - target| of two [B, frames, n_out] tensors -> [B] fp32 (ias_l1_rows: fixed order, a row's
+        result the same bits wherever it sits in the batch)."""
+        lib = _lib.load()
+        assert values.shape == target_values.shape and values.is_contiguous() and target_values.is_contiguous()
+        _lib.require_f32(values, target_values)
+        B = values.shape[0]
+        n = values[0].numel()
+        nch = lib.ias_l1_rows_partials_count(n)
+        _lib.check(min(nch, 0), "ias_l1_rows_partials_count")
+        partials = torch.empty((B, nch), dtype=torch.float64, device=values.device)
+        out = torch.empty(B, dtype=torch.float32, device=values.device)
+        _lib.check(lib.ias_l1_rows(_lib.ptr(values), _lib.ptr(target_values), B, n, _lib.ptr(partials), _lib.ptr(out),
+                                   _lib.stream()), "ias_l1_rows")
+        return out
+
+
 class _L1LossFn(torch.autograd.Function):
     """mean |V(audio) - target| with the fused HIP forward and the HIP adjoint w.r.t. the audio."""
 
@@ -235,6 +252,47 @@ def _l1_loss(plan, audio, target_values, value_mode, rowpeak=None, reduce_stream
         return _L1LossFn.apply(audio, plan, target_values, value_mode)
     return plan.loss_sums(audio, target_values, value_mode, LOSS_L1, mean_scale=1.0 / target_values.numel(),
                           rowpeak=rowpeak, reduce_stream=reduce_stream)
+
+
+class _L1RowsFn(torch.autograd.Function):
+    """[B] per-sound mean |V(audio) - target| (the values pass, then ias_l1_rows) with the HIP adjoint w.r.t. the audio for
+    a cotangent per row (ias_stft_loss_backward_rows)."""
+
+    @staticmethod
+    def forward(ctx, audio, plan, target_values, value_mode):
+        a = plan._audio2d(audio)
+        assert target_values.shape == (a.shape[0], plan.num_frames(a.shape[1]), plan.n_out)
+        ctx.plan, ctx.value_mode, ctx.shape = plan, value_mode, audio.shape
+        ctx.save_for_backward(a, target_values)
+        return plan.l1_rows(plan.values(a, value_mode), target_values)
+
+    @staticmethod
+    def backward(ctx, g_rows):
+        a, target = ctx.saved_tensors
+        plan = ctx.plan
+        lib = _lib.load()
+        B, T = a.shape
+        F = plan.num_frames(T)
+        mel = plan.n_mels is not None
+        frame_grad = torch.empty((B, F, plan.n_fft), dtype=torch.float32, device=a.device)
+        g_audio = torch.empty_like(a)
+        g = g_rows.to(torch.float32).reshape(B).contiguous()
+        st = lib.ias_stft_loss_backward_rows(
+            _lib.ptr(a), _lib.ptr(plan.window), _lib.ptr(plan.tables), _lib.ptr(plan.mel_start) if mel else None,
+            _lib.ptr(plan.mel_count) if mel else None, _lib.ptr(plan.mel_woff) if mel else None,
+            _lib.ptr(plan.mel_w) if mel else None, int(plan.mel_w.numel()) if mel else 0, _lib.ptr(target), _lib.ptr(g),
+            _lib.ptr(frame_grad), _lib.ptr(g_audio), B, T, plan.n_fft, plan.hop_length, plan.n_out,
+            2 if ctx.value_mode == VALUE_POWER else 1, 1.0 / (F * plan.n_out), _lib.stream())
+        _lib.check(st, "ias_stft_loss_backward_rows")
+        return g_audio.reshape(ctx.shape), None, None, None
+
+
+def _l1_rows(plan, audio, target_values, value_mode):
+    assert value_mode in (VALUE_POWER, VALUE_MAG)
+    if torch.is_grad_enabled() and audio.requires_grad:
+        return _L1RowsFn.apply(audio, plan, target_values, value_mode)
+    a = plan._audio2d(audio)
+    return plan.l1_rows(plan.values(a, value_mode), target_values)
 
 
 class MelSpectrogram(nn.Module):
@@ -280,6 +338,13 @@ class MelSpectrogramL1(nn.Module):
             target_mel = self.target(target_audio)
         return _l1_loss(self.mel.plan, audio, target_mel.detach(), self.mel.value_mode, rowpeak, reduce_stream)
 
+    def per_item(self, audio, target_audio=None, target_mel=None):
+        """[B] fp32: the mel L1 of each sound on its own (mean over its frames and bands), differentiable w.r.t. the
+        audio.  Its mean over the batch is ``forward``'s loss; a row's value does not depend on the other rows."""
+        if target_mel is None:
+            target_mel = self.target(target_audio)
+        return _l1_rows(self.mel.plan, audio, target_mel.detach().contiguous(), self.mel.value_mode)
+
 
 class STFTL1(nn.Module):
     """mean | |STFT(a)|^p - |STFT(b)|^p |  (BASELINE config #1 "STFT L1 loss")."""
@@ -293,6 +358,18 @@ class STFTL1(nn.Module):
     def forward(self, audio, target_audio):
         tgt = self.plan.values(target_audio.detach(), self.value_mode)
         return _l1_loss(self.plan, audio, tgt, self.value_mode)
+
+    def target(self, target_audio):
+        """Cacheable frames-major STFT values of the target audio (``per_item(..., target_values=)``)."""
+        return self.plan.values(target_audio.detach(), self.value_mode)
+
+    def per_item(self, audio, target_audio=None, target_values=None):
+        """[B] fp32: the STFT L1 of each sound on its own, differentiable w.r.t. the audio (see
+        ``MelSpectrogramL1.per_item``)."""
+        assert (target_audio is None) != (target_values is None), "give the target audio or its cached values"
+        if target_values is None:
+            target_values = self.target(target_audio)
+        return _l1_rows(self.plan, audio, target_values.detach().contiguous(), self.value_mode)
 
 
 class MultiResolutionSTFTLoss(nn.Module):

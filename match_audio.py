@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""Sound matching entry point: fit the 78 Voice parameters to WAV files.
+
+    python match_audio.py in1.wav in2.wav --steps 200 --out DIR [--init center|random] [key=value ...]
+
+``key=value`` are config overrides as for pretrain.py / audio_to_params.py (``torchsynth.rate``,
+``torchsynth.buffer_size_seconds``, ``mel.*``); the matcher's own settings are flags.  Input WAVs are 16- or 32-bit
+integer PCM at ``torchsynth.rate`` (no resampling); several channels are averaged; a file longer or shorter than the
+synth buffer is cropped or zero-padded, with a warning.  Per input NAME the script writes NAME.params.json (every
+parameter in 0..1 and in its own units, the initial and final loss) and NAME.match.wav (the best render, 16-bit PCM)."""
+import argparse
+import json
+import os
+import sys
+import wave
+import warnings
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+
+def read_wav(path, rate):
+    """-> mono float32 samples in [-1, 1).  16- or 32-bit integer PCM, channels averaged; any rate but ``rate`` is
+    refused (ValueError)."""
+    with wave.open(path, "rb") as w:
+        nch, width, sr, nframes = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
+        raw = w.readframes(nframes)
+    if sr != rate:
+        raise ValueError(f"{path}: sample rate {sr} Hz, the synth runs at {rate} Hz (torchsynth.rate); resample the file "
+                         f"or pass torchsynth.rate={sr}")
+    if width == 2:
+        x = np.frombuffer(raw, dtype="<i2").astype(np.float64) / 32768.0
+    elif width == 4:
+        x = np.frombuffer(raw, dtype="<i4").astype(np.float64) / 2147483648.0
+    else:
+        raise ValueError(f"{path}: {8 * width}-bit samples; only 16- and 32-bit integer PCM are read")
+    return x.reshape(-1, nch).mean(axis=1).astype(np.float32)
+
+
+def write_wav(path, samples, rate):
+    """Mono 16-bit PCM, the inverse of ``read_wav``'s scale (samples clipped to [-1, 32767 / 32768])."""
+    x = np.asarray(samples, dtype=np.float64)
+    pcm = np.clip(np.round(x * 32768.0), -32768, 32767).astype("<i2")
+    with wave.open(path, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(rate))
+        w.writeframes(pcm.tobytes())
+
+
+def fit_length(x, length, name="input"):
+    """Crop or zero-pad to ``length`` samples, with a warning when the length changes."""
+    if len(x) > length:
+        warnings.warn(f"{name}: {len(x)} samples, cropped to the synth buffer of {length}")
+        return x[:length]
+    if len(x) < length:
+        warnings.warn(f"{name}: {len(x)} samples, zero-padded to the synth buffer of {length}")
+        return np.concatenate([x, np.zeros(length - len(x), dtype=x.dtype)])
+    return x
+
+
+def params_record(params01_row):
+    """[78] params in 0..1 -> list of {module, name, value01, value} (value in the parameter's own units)."""
+    from inverse_audio_synthesis_amd import voice_spec as S
+    from inverse_audio_synthesis_amd.voice_grad import _from_0to1
+    p = params01_row.detach().double().cpu().reshape(1, -1)
+    units = _from_0to1(p)[0]
+    return [{"module": m, "name": n, "value01": float(p[0, i]), "value": float(units[i])}
+            for i, (m, n, *_r) in enumerate(S.PARAMS)]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("inputs", nargs="+", help="WAV files (16/32-bit PCM) and key=value config overrides")
+    ap.add_argument("--out", required=True, help="output directory")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--init", choices=("center", "random"), default="center")
+    ap.add_argument("--loss", choices=("mel_l1", "stft_l1"), default="mel_l1")
+    ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--beta1", type=float, default=0.9)
+    ap.add_argument("--beta2", type=float, default=0.999)
+    ap.add_argument("--eps", type=float, default=1e-8)
+    ap.add_argument("--batch-size", type=int, default=128, help="sounds fitted at once (at most)")
+    ap.add_argument("--seed", type=int, default=0, help="seed of --init random")
+    args = ap.parse_args(argv)
+    files = [a for a in args.inputs if "=" not in a]
+    overrides = [a for a in args.inputs if "=" in a]
+    if not files:
+        ap.error("no input WAV files")
+
+    import torch
+    from inverse_audio_synthesis_amd.config import load_config
+    from inverse_audio_synthesis_amd.match import SoundMatcher
+    from inverse_audio_synthesis_amd.voice import SynthConfig, Voice
+    cfg = load_config(os.path.join(ROOT, "conf"), "config", overrides)
+    rate = int(cfg.torchsynth.rate)
+    dev = torch.device("cuda:0")
+    batch = max(1, min(len(files), int(args.batch_size)))
+    voice = Voice(SynthConfig(batch_size=batch, sample_rate=rate, buffer_size_seconds=cfg.torchsynth.buffer_size_seconds,
+                              reproducible=cfg.torchsynth.reproducible)).to(dev)
+    T = voice.synthconfig.buffer_size
+    try:
+        target = np.stack([fit_length(read_wav(f, rate), T, f) for f in files])
+    except ValueError as e:
+        sys.exit(f"match_audio.py: {e}")
+    target = torch.from_numpy(target).to(dev)
+    if args.init == "random":
+        init = torch.rand((len(files), 78), generator=torch.Generator().manual_seed(args.seed)).to(dev)
+    else:
+        init = None
+    matcher = SoundMatcher(voice, loss=args.loss, mel_kwargs=dict(cfg.mel), lr=args.lr, betas=(args.beta1, args.beta2),
+                           eps=args.eps)
+    res = matcher.fit(target, init_params01=init, steps=args.steps, return_audio=True)
+    os.makedirs(args.out, exist_ok=True)
+    audio = res.audio.cpu().numpy()
+    for i, f in enumerate(files):
+        name = os.path.splitext(os.path.basename(f))[0]
+        rec = {"input": os.path.basename(f), "loss_kind": args.loss, "steps": args.steps,
+               "initial_loss": float(res.initial_loss[i]), "final_loss": float(res.loss[i]),
+               "skipped": int(res.skipped[i]), "params": params_record(res.params01[i])}
+        with open(os.path.join(args.out, name + ".params.json"), "w") as fh:
+            json.dump(rec, fh, indent=1)
+        write_wav(os.path.join(args.out, name + ".match.wav"), audio[i], rate)
+        print(json.dumps({"input": rec["input"], "initial_loss": rec["initial_loss"], "final_loss": rec["final_loss"]}),
+              flush=True)
+
+
+if __name__ == "__main__":
+    main()
