@@ -333,6 +333,39 @@ int ias_match_adam_step(float* params, const float* grad, float* m, float* v, in
                         double* best_loss, float* best_params, const unsigned char* free_cols, const unsigned char* active,
                         int* skipped, int B, int P, float lr, float beta1, float beta2, float eps, void* stream);
 
+/* Per-sound MR-STFT (MultiResolutionSTFTLoss.per_item): L_b = (1/nres) sum_k [sqrt(sum_row (T - V)^2) / sqrt(sum_row T^2)
+ * + sum_row |ln V - ln T| / count_k] with V, T = sqrt(max(|X|^2, eps)) of the prediction and the target (ias_stft
+ * VALUE_MAG_CLAMPED) and count_k = F_k * n_out_k, the batch loss applied to row b alone.  Same per-row contract as
+ * ias_l1_rows: a row's results do not depend on its position in the batch or on the other rows (same bits).
+ * ias_mrstft_rows: sums [B][3] (device fp64) = {sum (T - V)^2, sum T^2, sum |ln V - ln T|} over rows of n floats
+ *   (values, target [B,n] fp32; the log terms as in the batch loss kernels: the difference of two log2, ln 2 applied to
+ *   the row's sum).  partials [B][ias_mrstft_rows_partials_count(n)][3] doubles: scratch (folded in chunk order).
+ * ias_mrstft_rows_total: out[B] (device fp32) = L_b; sums_host: HOST array of nres <= 8 device pointers to the
+ *   resolutions' ias_mrstft_rows sums, counts_host: HOST doubles count_k.  ias_mrstft_total's expression per row.
+ * ias_mrstft_coef_rows: coef [B][2] (device doubles) = ias_mrstft_coef's pair per row with g = g_rows[b] (device fp32 [B],
+ *   count = count_k): {g / (nres sqrt(s[b][0]) sqrt(s[b][1])) (0 when the denominator is 0), g / (nres count)}, {0, 0}
+ *   where g_rows[b] == 0.
+ * ias_stft_loss_backward_mrstft_rows / ias_stft_grad_frames_mrstft_rows / ias_stft_grad_spans_mrstft_rows:
+ *   ias_stft_loss_backward / ias_stft_grad_frames / ias_stft_grad_spans for loss_mode 2 (power 1, linear bins, n_out =
+ *   n_fft/2+1, no g_loss) with coef_rows [B][2] (ias_mrstft_coef_rows) read at the row being processed; the span plan is
+ *   the one ias_stft_grad_span_plan returns, and the spans finish with ias_stft_grad_combine (g_loss NULL).  Rows whose
+ *   pair is {0, 0} get exactly 0. */
+int ias_mrstft_rows_partials_count(long long n);
+int ias_mrstft_rows(const float* values, const float* target, int B, long long n, double* partials, double* sums,
+                    void* stream);
+int ias_mrstft_rows_total(const double* const* sums_host, const double* counts_host, int nres, int B, float* out,
+                          void* stream);
+int ias_mrstft_coef_rows(const double* sums, const float* g_rows, double count, int nres, int B, double* coef, void* stream);
+int ias_stft_loss_backward_mrstft_rows(const float* audio, const float* window, const float* tables, const float* target,
+                                       const double* coef_rows, float* frame_grad, float* g_audio, int B, int T, int n_fft,
+                                       int hop, int n_out, float eps, void* stream);
+int ias_stft_grad_frames_mrstft_rows(const float* audio, const float* tables, int n_out, const float* target,
+                                     const double* coef_rows, float* frame_grad, int B, int T, int n_fft, int hop,
+                                     float eps, void* stream);
+int ias_stft_grad_spans_mrstft_rows(const float* audio, const float* tables, int n_out, const float* target,
+                                    const double* coef_rows, float* chunk_spans, int B, int T, int n_fft, int hop,
+                                    float eps, int* plan_host, void* stream);
+
 /* sums[3] (doubles) = column sums of partials [n][3], fixed order (deterministic); when mean_out is not
  * NULL also mean_out[0] = (float)(sums[0] * scale). */
 int ias_reduce_partials(const double* partials, long long n, double* sums, double scale, float* mean_out,

@@ -91,6 +91,13 @@ SYMBOLS = {
     "ias_l1_rows": (_I, [_P, _P, _I, _LL, _P, _P, _P]),
     "ias_stft_loss_backward_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "ias_match_adam_step": (_I, [_P] * 11 + [_I, _I, _F, _F, _F, _F, _P]),
+    "ias_mrstft_rows_partials_count": (_I, [_LL]),
+    "ias_mrstft_rows": (_I, [_P, _P, _I, _LL, _P, _P, _P]),
+    "ias_mrstft_rows_total": (_I, [_P, _P, _I, _I, _P, _P]),
+    "ias_mrstft_coef_rows": (_I, [_P, _P, _c.c_double, _I, _I, _P, _P]),
+    "ias_stft_loss_backward_mrstft_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
+    "ias_stft_grad_frames_mrstft_rows": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "ias_stft_grad_spans_mrstft_rows": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P]),
     "ias_vicreg_workspace_bytes": (_LL, [_I, _I]),
     "ias_vicreg_colstats_offset": (_LL, [_I, _I]),
     "ias_vicreg_loss": (_I, [_P, _P, _P, _P, _LL, _I, _I, _I, _F, _F, _F, _P]),

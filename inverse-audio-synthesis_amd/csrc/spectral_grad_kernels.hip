@@ -84,7 +84,7 @@ struct SgArgs {
   int T, F, N, log2n, hop, n_out, power2;
   int mel_nnz;            // entries of mel_w (0 without a mel projection)
   int loss_mode;          // 1: scale * sum |V - t|;  2: MR-STFT term, V = sqrt(max(|X|^2, eps))
-  const double* coef;     // loss_mode 2: device [2] = {c0, c1}: gO = c0 (V - t) + c1 sign(V - t) / V
+  const double* coef;     // loss_mode 2: device [2] = {c0, c1}: gO = c0 (V - t) + c1 sign(V - t) / V  (CROW: [B][2])
   float scale, eps;
 };
 
@@ -100,6 +100,8 @@ __device__ __forceinline__ sg_cpx sg_frame_bin(const sg_cpx* Z, int k, int N, in
                     : make_float2(0.5f * (z.y + zc.y), -0.5f * (z.x - zc.x));
 }
 
+// CROW: coef is [B][2], the pair of row b = blockIdx.y (ias_stft_loss_backward_mrstft_rows).
+template <bool CROW>
 __global__ __launch_bounds__(SG_THREADS) void stft_grad_frames_kernel(SgArgs g) {
   extern __shared__ __attribute__((aligned(16))) float sg_smem[];
   const int N = g.N, NB = N / 2 + 1, tid = threadIdx.x, b = blockIdx.y;
@@ -180,7 +182,8 @@ __global__ __launch_bounds__(SG_THREADS) void stft_grad_frames_kernel(SgArgs g) 
       const float d = v - g.target[((size_t)b * g.F + fa + r) * g.n_out + o];
       const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
       // MR-STFT: spectral convergence ||T - V||_F / ||T||_F and mean |log V - log T| (log is monotone: sign(V - T))
-      go = g.loss_mode == 2 ? (float)g.coef[0] * d + (float)g.coef[1] * sg / v : sg * g.scale;
+      const double* cf = CROW ? g.coef + 2 * (size_t)b : g.coef;
+      go = g.loss_mode == 2 ? (float)cf[0] * d + (float)cf[1] * sg / v : sg * g.scale;
     }
     sGO[r * SO + o] = go;
   }
@@ -414,8 +417,16 @@ extern "C" int ias_stft_grad_spans(const float* audio, const float* tables, cons
                                    const int* mel_woff, const float* mel_w, int mel_nnz, int n_out, const float* target,
                                    const double* coef, float* chunk_spans, int B, int T, int n_fft, int hop, int power,
                                    int loss_mode, float scale, float eps, int* plan_host, void* stream);
+extern "C" int ias_stft_grad_frames_mrstft_rows(const float* audio, const float* tables, int n_out, const float* target,
+                                                const double* coef_rows, float* frame_grad, int B, int T, int n_fft,
+                                                int hop, float eps, void* stream);
+extern "C" int ias_stft_grad_spans_mrstft_rows(const float* audio, const float* tables, int n_out, const float* target,
+                                               const double* coef_rows, float* chunk_spans, int B, int T, int n_fft,
+                                               int hop, float eps, int* plan_host, void* stream);
 
-template <bool ROWS>
+// ROWS: g_loss is [B] (one cotangent per row, loss_mode 1).  CROW: coef is [B][2] (one pair per row, loss_mode 2,
+// g_loss NULL).
+template <bool ROWS, bool CROW>
 static int stft_loss_backward(const float* audio, const float* window, const float* tables, const int* mel_start,
                               const int* mel_count, const int* mel_woff, const float* mel_w, int mel_nnz,
                               const float* target, const float* g_loss, const double* coef, float* frame_grad,
@@ -440,9 +451,11 @@ static int stft_loss_backward(const float* audio, const float* window, const flo
     static const bool nospan = ias_diag_env("IAS_STFT_GRAD_NOSPAN") != nullptr && atoi(ias_diag_env("IAS_STFT_GRAD_NOSPAN")) != 0;
     if (!nospan && (reinterpret_cast<uintptr_t>(frame_grad) & 15) == 0) {
       int plan[3] = {0, 0, 0};
-      const int rs = ias_stft_grad_spans(audio, tables, mel_start, mel_count, mel_woff, mel_w, mel ? mel_nnz : 0, n_out,
-                                         target, coef, frame_grad, B, T, n_fft, hop, power, loss_mode, scale, eps, plan,
-                                         stream_);
+      const int rs = CROW ? ias_stft_grad_spans_mrstft_rows(audio, tables, n_out, target, coef, frame_grad, B, T, n_fft,
+                                                            hop, eps, plan, stream_)
+                          : ias_stft_grad_spans(audio, tables, mel_start, mel_count, mel_woff, mel_w, mel ? mel_nnz : 0,
+                                                n_out, target, coef, frame_grad, B, T, n_fft, hop, power, loss_mode,
+                                                scale, eps, plan, stream_);
       if (rs == IAS_OK) {
         hipLaunchKernelGGL(stft_grad_combine_kernel<ROWS>, dim3((T + SG_THREADS - 1) / SG_THREADS, B), dim3(SG_THREADS), 0,
                            stream, frame_grad, g_loss, g_audio, T, F, n_fft, hop, plan[0], plan[1], plan[2]);
@@ -450,8 +463,11 @@ static int stft_loss_backward(const float* audio, const float* window, const flo
       }
       if (rs != IAS_ERR_UNSUPPORTED) return rs;
     }
-    const int rc = ias_stft_grad_frames(audio, tables, mel_start, mel_count, mel_woff, mel_w, mel ? mel_nnz : 0, n_out,
-                                        target, coef, frame_grad, B, T, n_fft, hop, power, loss_mode, scale, eps, stream_);
+    const int rc = CROW ? ias_stft_grad_frames_mrstft_rows(audio, tables, n_out, target, coef, frame_grad, B, T, n_fft, hop,
+                                                           eps, stream_)
+                        : ias_stft_grad_frames(audio, tables, mel_start, mel_count, mel_woff, mel_w, mel ? mel_nnz : 0,
+                                               n_out, target, coef, frame_grad, B, T, n_fft, hop, power, loss_mode, scale,
+                                               eps, stream_);
     if (rc != IAS_OK) return rc;
     hipLaunchKernelGGL(stft_grad_ola_kernel<ROWS>, dim3((T + SG_THREADS - 1) / SG_THREADS, B), dim3(SG_THREADS), 0, stream,
                        frame_grad, g_loss, g_audio, T, F, n_fft, hop);
@@ -469,9 +485,9 @@ static int stft_loss_backward(const float* audio, const float* window, const flo
                      sizeof(float) * (6 * (size_t)(NB + 3) + 2 * ((n_out + 3) & ~3) + ((g.mel_nnz + 3) & ~3)) +
                      sizeof(int) * 3 * (size_t)(mel ? n_out : 0);
   if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)stft_grad_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)stft_grad_frames_kernel<CROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int pairs = (F + 1) / 2;
-  hipLaunchKernelGGL(stft_grad_frames_kernel, dim3((pairs + SG_PAIRS - 1) / SG_PAIRS, B), dim3(SG_THREADS), lds, stream,
+  hipLaunchKernelGGL(stft_grad_frames_kernel<CROW>, dim3((pairs + SG_PAIRS - 1) / SG_PAIRS, B), dim3(SG_THREADS), lds, stream,
                      g);
   hipLaunchKernelGGL(stft_grad_ola_kernel<ROWS>, dim3((T + SG_THREADS - 1) / SG_THREADS, B), dim3(SG_THREADS), 0, stream,
                      frame_grad, g_loss, g_audio, T, F, n_fft, hop);
@@ -483,8 +499,9 @@ extern "C" int ias_stft_loss_backward(const float* audio, const float* window, c
                                       const float* target, const float* g_loss, const double* coef, float* frame_grad,
                                       float* g_audio, int B, int T, int n_fft, int hop, int n_out, int power,
                                       int loss_mode, float scale, float eps, void* stream_) {
-  return stft_loss_backward<false>(audio, window, tables, mel_start, mel_count, mel_woff, mel_w, mel_nnz, target, g_loss,
-                                   coef, frame_grad, g_audio, B, T, n_fft, hop, n_out, power, loss_mode, scale, eps, stream_);
+  return stft_loss_backward<false, false>(audio, window, tables, mel_start, mel_count, mel_woff, mel_w, mel_nnz, target,
+                                          g_loss, coef, frame_grad, g_audio, B, T, n_fft, hop, n_out, power, loss_mode, scale,
+                                          eps, stream_);
 }
 
 // d (sum_b g_rows[b] L_b) / d audio for the per-sound L1 losses L_b = scale * sum over row b of |V - target| (scale
@@ -496,8 +513,22 @@ extern "C" int ias_stft_loss_backward_rows(const float* audio, const float* wind
                                            float* frame_grad, float* g_audio, int B, int T, int n_fft, int hop, int n_out,
                                            int power, float scale, void* stream_) {
   if (!g_rows) return IAS_ERR_ARG;
-  return stft_loss_backward<true>(audio, window, tables, mel_start, mel_count, mel_woff, mel_w, mel_nnz, target, g_rows,
-                                  nullptr, frame_grad, g_audio, B, T, n_fft, hop, n_out, power, 1, scale, 0.0f, stream_);
+  return stft_loss_backward<true, false>(audio, window, tables, mel_start, mel_count, mel_woff, mel_w, mel_nnz, target,
+                                         g_rows, nullptr, frame_grad, g_audio, B, T, n_fft, hop, n_out, power, 1,
+                                         scale, 0.0f, stream_);
+}
+
+// d (sum_b L_b) / d audio for one resolution of the per-sound MR-STFT losses, with the row's cotangent folded into its
+// coefficient pair: coef_rows [B][2] device doubles (ias_mrstft_coef_rows), otherwise as ias_stft_loss_backward
+// (loss_mode 2: power 1, linear bins).  The same frame / span kernels read the pair of the row they work on; rows whose
+// pair is {0, 0} get exactly 0.
+extern "C" int ias_stft_loss_backward_mrstft_rows(const float* audio, const float* window, const float* tables,
+                                                  const float* target, const double* coef_rows, float* frame_grad,
+                                                  float* g_audio, int B, int T, int n_fft, int hop, int n_out, float eps,
+                                                  void* stream_) {
+  if (!coef_rows) return IAS_ERR_ARG;
+  return stft_loss_backward<false, true>(audio, window, tables, nullptr, nullptr, nullptr, nullptr, 0, target, nullptr,
+                                         coef_rows, frame_grad, g_audio, B, T, n_fft, hop, n_out, 1, 2, 0.0f, eps, stream_);
 }
 
 // ------------------------------------------------------------------------------------------------ scalar glue

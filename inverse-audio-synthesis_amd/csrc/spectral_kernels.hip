@@ -1087,7 +1087,11 @@ struct SgwArgs {
 // touches leave the ring for the chunk's span  frame_grad[chunk][L], L = (G - 1) hop + n_fft.  The [B,F,n_fft] tensor
 // (8.5 - 10 floats per audio sample, written here and read again by stft_grad_ola_kernel) shrinks to ~1.2 - 1.5
 // floats per sample; stft_grad_combine_kernel adds the two chunks that meet at a sample, lower chunk first.
-template <int LOG2N, bool MEL, bool SPAN>
+//
+// CROW (loss_mode 2 only): coef holds one pair per row, [B][2] (the per-sound MR-STFT losses, ias_stft_grad_spans_mrstft_rows);
+// a wave reads the pair of the row it is working on at the start of every chunk (a SPAN wave can walk chunks of several
+// rows).  A row whose pair is {0, 0} gets exactly 0.
+template <int LOG2N, bool MEL, bool SPAN, bool CROW>
 __global__ __launch_bounds__(256) void stft_grad_wave_kernel(const SgwArgs a) {
   constexpr int SP_WAVES = 4, SP_THREADS = 256;
   constexpr int NFFT = 1 << LOG2N, N2 = NFFT / 2, R = N2 / 64, NPAIR = 8 * R, NP_IT = (NPAIR + 63) / 64;
@@ -1137,7 +1141,7 @@ __global__ __launch_bounds__(256) void stft_grad_wave_kernel(const SgwArgs a) {
   __syncthreads();
   cpx* sA = s_scr + wave * SCR;
   float c0 = 0.0f, c1 = 0.0f;
-  if (a.loss_mode == 2) { c0 = (float)a.coef[0]; c1 = (float)a.coef[1]; }
+  if constexpr (!CROW) { if (a.loss_mode == 2) { c0 = (float)a.coef[0]; c1 = (float)a.coef[1]; } }
 
   // the three passes of stft_kernel: v = the lane's R points (64 n1 + lane) -> DFT in natural order, sA[IAS_S2_UP(k)]
   auto fft = [&](cpx (&v)[R]) {
@@ -1210,6 +1214,7 @@ __global__ __launch_bounds__(256) void stft_grad_wave_kernel(const SgwArgs a) {
   int b, f_lo, f_hi;
   if (SPAN) { b = c / a.cper; f_lo = (c - b * a.cper) * a.G; f_hi = min(f_lo + a.G, a.F); }
   else { b = blockIdx.y; f_lo = blockIdx.x * a.groups + wave; f_hi = min((int)blockIdx.x * a.groups + a.groups, a.F); }
+  if constexpr (CROW) { c0 = (float)a.coef[2 * (size_t)b]; c1 = (float)a.coef[2 * (size_t)b + 1]; }
   const float* arow = a.audio + (size_t)b * a.T;
   float* span = a.frame_grad + (size_t)c * a.L;
   for (int f = f_lo; f < f_hi; f += SPAN ? 1 : SP_WAVES) {
@@ -1393,7 +1398,8 @@ __global__ __launch_bounds__(256) void stft_grad_wave_kernel(const SgwArgs a) {
 // SPAN: as in stft_grad_wave_kernel (a wave walks a chunk of G consecutive frames, overlap-add in an LDS ring, hop % 4
 // == 0).  The ring is kept in 16-byte units q = sample / 4 at slot q ^ ((q >> 3) & 7): the lanes' units m = k1 + 8 d
 // (+ 64 e) are 8 apart for consecutive lanes, the swizzle spreads them over the banks.
-template <int SP_WAVES, bool SPAN>
+// CROW: per-row coefficient pairs, as in stft_grad_wave_kernel (read for every chunk or frame: both walk across rows).
+template <int SP_WAVES, bool SPAN, bool CROW>
 __global__ __launch_bounds__(64 * SP_WAVES, SPAN ? 2 : 3 * SP_WAVES / 8) void stft_grad2k_kernel(const SgwArgs a, int nframes, unsigned magicF) {
   constexpr int SP_THREADS = 64 * SP_WAVES, N2 = 1024, HALF = 512, NFFT = 2048, SCR = 64 * IAS_S2_ROW, NB = N2 + 1;
   constexpr int NTAB = 16 + 8 + 8 + 8 + 8 + 16;   // stft2's 2048 section + the window at the lane's OUTPUT samples
@@ -1419,7 +1425,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, SPAN ? 2 : 3 * SP_WAVES / 8) void st
   cpx* sA = s_scr + wave * SCR;
   const int k1 = lane >> 3, dd = lane & 7, kl = k1 + 8 * dd;
   float c0 = 0.0f, c1 = 0.0f;
-  if (a.loss_mode == 2) { c0 = (float)a.coef[0]; c1 = (float)a.coef[1]; }
+  if constexpr (!CROW) { if (a.loss_mode == 2) { c0 = (float)a.coef[0]; c1 = (float)a.coef[1]; } }
   auto bin_value = [&](float p) { return a.power2 ? p : __builtin_amdgcn_sqrtf(a.loss_mode == 2 ? fmaxf(p, a.eps) : p); };   // v_sqrt_f32
   auto value_grad = [&](float v, float t) {
     const float d = v - t;
@@ -1466,6 +1472,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, SPAN ? 2 : 3 * SP_WAVES / 8) void st
     if (fr0 >= a.F) { fr0 -= a.F; ++q0; }
     b = (int)q0; f_lo = fr0; f_hi = fr0 + 1;
   }
+  if constexpr (CROW) { c0 = (float)a.coef[2 * (size_t)b]; c1 = (float)a.coef[2 * (size_t)b + 1]; }
   f32x4* span = reinterpret_cast<f32x4*>(a.frame_grad + (size_t)c * a.L);   // SPAN (L % 4 == 0)
   for (int fr = f_lo; fr < f_hi; ++fr) {
     const int fi = b * a.F + fr;
@@ -1616,7 +1623,8 @@ __global__ __launch_bounds__(64 * SP_WAVES, SPAN ? 2 : 3 * SP_WAVES / 8) void st
 // B), the inverse inputs Zin of both frames through the scratch in natural order, ONE more run of the three passes on
 // their conjugates, then frame A's lanes add their windowed samples into the ring, after them frame B's (frame order:
 // deterministic), and the 2 hop samples no later frame reaches leave the ring.
-template <int SP_WAVES>
+// CROW: per-row coefficient pairs, as in stft_grad_wave_kernel.
+template <int SP_WAVES, bool CROW>
 __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 2) void stft_grad512_kernel(const SgwArgs a) {
   constexpr int SP_THREADS = 64 * SP_WAVES, SCR = 64 * IAS_S2_ROW, NFFT = 512, N2 = 256, HALF = 128, NB = 257;
   constexpr int NTAB = 4 + 4 + 8 + 4 + 8;    // stft2h's tables + the window at the lane's OUTPUT samples
@@ -1642,7 +1650,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 2) void stft_grad512_kern
   float* ring = s_ring + wave * NFFT;
   const int slot = lane >> 3, dd = lane & 7, fr = lane >> 5, kl = (slot & 3) + 4 * dd;
   float c0 = 0.0f, c1 = 0.0f;
-  if (a.loss_mode == 2) { c0 = (float)a.coef[0]; c1 = (float)a.coef[1]; }
+  if constexpr (!CROW) { if (a.loss_mode == 2) { c0 = (float)a.coef[0]; c1 = (float)a.coef[1]; } }
   auto bin_value = [&](float p) { return a.power2 ? p : __builtin_amdgcn_sqrtf(a.loss_mode == 2 ? fmaxf(p, a.eps) : p); };
   auto value_grad = [&](float v, float t) {
     const float d = v - t;
@@ -1683,6 +1691,7 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 2) void stft_grad512_kern
   const int cstep = (int)gridDim.x * SP_WAVES;
   for (int c = (int)blockIdx.x * SP_WAVES + wave; c < a.nchunks; c += cstep) {
     const int b = c / a.cper, f_lo = (c - b * a.cper) * a.G, f_hi = min(f_lo + a.G, a.F);
+    if constexpr (CROW) { c0 = (float)a.coef[2 * (size_t)b]; c1 = (float)a.coef[2 * (size_t)b + 1]; }
     const float* arow = a.audio + (size_t)b * a.T;
     float* span = a.frame_grad + (size_t)c * a.L;
     for (int f = f_lo; f < f_hi; f += 2) {
@@ -1818,6 +1827,9 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES / 2) void stft_grad512_kern
 // coef: device doubles [2] (loss_mode 2, linear bins only).
 // plan != NULL: the SPAN kernels (overlap-add inside the kernel); frame_grad then receives B * plan[1] chunk spans of
 // plan[2] floats (plan[0] = frames per chunk), IAS_ERR_UNSUPPORTED when the shape does not allow it.
+// CROW: coef is [B][2] (one pair per row, loss_mode 2, linear bins); the chunk plan is the one of the shared-coefficient
+// kernels (their occupancy), so ias_stft_grad_span_plan answers for both.
+template <bool CROW>
 static int grad_frames_launch(const float* audio, const float* tables, const int* mel_start, const int* mel_count,
                               const int* mel_woff, const float* mel_w, int mel_nnz, int n_out, const float* target,
                               const double* coef, float* frame_grad, int B, int T, int n_fft, int hop, int power,
@@ -1826,6 +1838,7 @@ static int grad_frames_launch(const float* audio, const float* tables, const int
   if (B <= 0 || B > 65535 || hop <= 0) return IAS_ERR_ARG;
   if (n_fft != 512 && n_fft != 1024 && n_fft != 2048) return IAS_ERR_UNSUPPORTED;
   if ((power != 1 && power != 2) || (loss_mode != 1 && loss_mode != 2) || (!dry && loss_mode == 2 && !coef)) return IAS_ERR_ARG;
+  if (CROW && (loss_mode != 2 || power != 1 || mel_start != nullptr || mel_nnz > 0)) return IAS_ERR_ARG;
   const bool mel = mel_start != nullptr || (dry && mel_nnz > 0);
   if (!dry && mel && (!mel_count || !mel_woff || !mel_w || mel_nnz <= 0 || n_out <= 0 || loss_mode != 1)) return IAS_ERR_ARG;
   if (!mel && n_out != n_fft / 2 + 1) return IAS_ERR_ARG;
@@ -1873,13 +1886,13 @@ static int grad_frames_launch(const float* audio, const float* tables, const int
       if (dry) return IAS_OK;
       const long long need = ((long long)a.nchunks + W2 - 1) / W2;
       const int grid2 = (int)(need < (long long)ncu ? need : (long long)ncu);
-      (void)hipFuncSetAttribute((const void*)stft_grad2k_kernel<W2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-      hipLaunchKernelGGL((stft_grad2k_kernel<W2, true>), dim3(grid2), dim3(64 * W2), lds2, stream, a, B * F, 0u);
+      (void)hipFuncSetAttribute((const void*)stft_grad2k_kernel<W2, true, CROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+      hipLaunchKernelGGL((stft_grad2k_kernel<W2, true, CROW>), dim3(grid2), dim3(64 * W2), lds2, stream, a, B * F, 0u);
     } else {
       const long long need = ((long long)B * F + W2 - 1) / W2;
       const int grid2 = (int)(need < 2LL * ncu ? need : 2LL * ncu);
-      (void)hipFuncSetAttribute((const void*)stft_grad2k_kernel<W2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-      hipLaunchKernelGGL((stft_grad2k_kernel<W2, false>), dim3(grid2), dim3(64 * W2), lds2, stream, a, B * F,
+      (void)hipFuncSetAttribute((const void*)stft_grad2k_kernel<W2, false, CROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+      hipLaunchKernelGGL((stft_grad2k_kernel<W2, false, CROW>), dim3(grid2), dim3(64 * W2), lds2, stream, a, B * F,
                          (F == 1 ? 0xFFFFFFFFu /* 2^32 / 1 does not fit: q0 = fi - 1, which row_of's one-step correction fixes */ : (unsigned)(0x100000000ULL / (unsigned long long)F)));
     }
     return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
@@ -1888,14 +1901,15 @@ static int grad_frames_launch(const float* audio, const float* tables, const int
   if (n_fft == 512 && span && !mel && !v1_512) {
     constexpr int W5 = 8;
     const size_t lds5 = sizeof(cpx) * (W5 * 64 * IAS_S2_ROW) + sizeof(float) * W5 * 512;
-    (void)hipFuncSetAttribute((const void*)stft_grad512_kernel<W5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5);
+    (void)hipFuncSetAttribute((const void*)stft_grad512_kernel<W5, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5);
+    if (CROW) (void)hipFuncSetAttribute((const void*)stft_grad512_kernel<W5, CROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5);
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, stft_grad512_kernel<W5>, 64 * W5, lds5) != hipSuccess || nb < 1) nb = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, stft_grad512_kernel<W5, false>, 64 * W5, lds5) != hipSuccess || nb < 1) nb = 1;
     if (!make_plan((long long)ncu * nb * W5)) return IAS_ERR_UNSUPPORTED;
     if (dry) return IAS_OK;
     const long long need = ((long long)a.nchunks + W5 - 1) / W5;
     const int grid5 = (int)(need < (long long)ncu * nb ? need : (long long)ncu * nb);
-    hipLaunchKernelGGL((stft_grad512_kernel<W5>), dim3(grid5), dim3(64 * W5), lds5, stream, a);
+    hipLaunchKernelGGL((stft_grad512_kernel<W5, CROW>), dim3(grid5), dim3(64 * W5), lds5, stream, a);
     return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
   }
   const int R = n_fft / 128, scr = 8 * R * IAS_S2_ROW, np_it = (8 * R + 63) / 64, nunp = (n_fft / 4) / 64 + 1;
@@ -1909,12 +1923,17 @@ static int grad_frames_launch(const float* audio, const float* tables, const int
   dim3 grid((F + g - 1) / g, B), block(256);
 #define IAS_SGW_LAUNCH(LOG2N, MEL, SPAN)                                                                          \
   do {                                                                                                             \
-    if (lds + lds_static > 48 * 1024)                                                                              \
-      (void)hipFuncSetAttribute((const void*)stft_grad_wave_kernel<LOG2N, MEL, SPAN>,                              \
+    if (lds + lds_static > 48 * 1024) {                                                                            \
+      (void)hipFuncSetAttribute((const void*)stft_grad_wave_kernel<LOG2N, MEL, SPAN, false>,                       \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                             \
+      if (CROW)                                                                                                    \
+        (void)hipFuncSetAttribute((const void*)stft_grad_wave_kernel<LOG2N, MEL, SPAN, CROW>,                      \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
+    }                                                                                                              \
     if (SPAN) {                                                                                                    \
       int nb = 0;                                                                                                  \
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, stft_grad_wave_kernel<LOG2N, MEL, SPAN>, 256, lds) !=  \
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, stft_grad_wave_kernel<LOG2N, MEL, SPAN, false>, 256,   \
+                                                       lds) !=                                                     \
               hipSuccess || nb < 1)                                                                                \
         nb = 1;                                                                                                    \
       if (!make_plan((long long)ncu * nb * 4)) return IAS_ERR_UNSUPPORTED;                                         \
@@ -1922,7 +1941,7 @@ static int grad_frames_launch(const float* audio, const float* tables, const int
       const long long need = ((long long)a.nchunks + 3) / 4;                                                       \
       grid = dim3((unsigned)(need < (long long)ncu * nb ? need : (long long)ncu * nb));                            \
     }                                                                                                              \
-    hipLaunchKernelGGL((stft_grad_wave_kernel<LOG2N, MEL, SPAN>), grid, block, lds, stream, a);                    \
+    hipLaunchKernelGGL((stft_grad_wave_kernel<LOG2N, MEL, SPAN, CROW>), grid, block, lds, stream, a);              \
   } while (0)
 #define IAS_SGW_PICK(MEL, SPAN)                                                                                    \
   do {                                                                                                             \
@@ -1930,8 +1949,12 @@ static int grad_frames_launch(const float* audio, const float* tables, const int
     else if (n_fft == 1024) IAS_SGW_LAUNCH(10, MEL, SPAN);                                                         \
     else IAS_SGW_LAUNCH(11, MEL, SPAN);                                                                            \
   } while (0)
-  if (mel) { if (span) IAS_SGW_PICK(true, true); else IAS_SGW_PICK(true, false); }
-  else { if (span) IAS_SGW_PICK(false, true); else IAS_SGW_PICK(false, false); }
+  if constexpr (!CROW) {
+    if (mel) { if (span) IAS_SGW_PICK(true, true); else IAS_SGW_PICK(true, false); }
+    else { if (span) IAS_SGW_PICK(false, true); else IAS_SGW_PICK(false, false); }
+  } else {
+    if (span) IAS_SGW_PICK(false, true); else IAS_SGW_PICK(false, false);
+  }
 #undef IAS_SGW_PICK
 #undef IAS_SGW_LAUNCH
   return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
@@ -1941,8 +1964,8 @@ extern "C" int ias_stft_grad_frames(const float* audio, const float* tables, con
                                     const int* mel_woff, const float* mel_w, int mel_nnz, int n_out, const float* target,
                                     const double* coef, float* frame_grad, int B, int T, int n_fft, int hop, int power,
                                     int loss_mode, float scale, float eps, void* stream_) {
-  return grad_frames_launch(audio, tables, mel_start, mel_count, mel_woff, mel_w, mel_nnz, n_out, target, coef, frame_grad,
-                            B, T, n_fft, hop, power, loss_mode, scale, eps, nullptr, (hipStream_t)stream_);
+  return grad_frames_launch<false>(audio, tables, mel_start, mel_count, mel_woff, mel_w, mel_nnz, n_out, target, coef,
+                                   frame_grad, B, T, n_fft, hop, power, loss_mode, scale, eps, nullptr, (hipStream_t)stream_);
 }
 
 // The chunk plan ias_stft_grad_spans will use for this shape (the device's occupancy enters it), without launching:
@@ -1950,8 +1973,8 @@ extern "C" int ias_stft_grad_frames(const float* audio, const float* tables, con
 extern "C" int ias_stft_grad_span_plan(int B, int T, int n_fft, int hop, int mel_nnz, int n_out, int* plan_host) {
   if (!plan_host) return IAS_ERR_ARG;
   if (mel_nnz > 0 && (n_out <= 0 || n_out > n_fft / 2 + 1)) return IAS_ERR_ARG;
-  return grad_frames_launch(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mel_nnz, n_out, nullptr, nullptr, nullptr,
-                            B, T, n_fft, hop, 1, 1, 1.0f, 0.0f, plan_host, nullptr, true);
+  return grad_frames_launch<false>(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mel_nnz, n_out, nullptr, nullptr,
+                                   nullptr, B, T, n_fft, hop, 1, 1, 1.0f, 0.0f, plan_host, nullptr, true);
 }
 
 // The same with the overlap-add inside the kernel: chunk_spans (B * plan[1] * plan[2] floats, 16-byte aligned) receives
@@ -1963,8 +1986,28 @@ extern "C" int ias_stft_grad_spans(const float* audio, const float* tables, cons
                                    const double* coef, float* chunk_spans, int B, int T, int n_fft, int hop, int power,
                                    int loss_mode, float scale, float eps, int* plan_host, void* stream_) {
   if (!plan_host || (reinterpret_cast<uintptr_t>(chunk_spans) & 15) != 0) return IAS_ERR_ARG;
-  return grad_frames_launch(audio, tables, mel_start, mel_count, mel_woff, mel_w, mel_nnz, n_out, target, coef, chunk_spans,
-                            B, T, n_fft, hop, power, loss_mode, scale, eps, plan_host, (hipStream_t)stream_);
+  return grad_frames_launch<false>(audio, tables, mel_start, mel_count, mel_woff, mel_w, mel_nnz, n_out, target, coef,
+                                   chunk_spans, B, T, n_fft, hop, power, loss_mode, scale, eps, plan_host,
+                                   (hipStream_t)stream_);
+}
+
+// The per-row-coefficient forms of the two entries above for one resolution of the per-sound MR-STFT losses
+// (MultiResolutionSTFTLoss.per_item): loss_mode 2, power 1, linear bins (n_out = n_fft / 2 + 1), coef_rows [B][2] device
+// doubles (ias_mrstft_coef_rows), read at the row being processed.  A row whose pair is {0, 0} gets exactly 0.
+extern "C" int ias_stft_grad_frames_mrstft_rows(const float* audio, const float* tables, int n_out, const float* target,
+                                                const double* coef_rows, float* frame_grad, int B, int T, int n_fft,
+                                                int hop, float eps, void* stream_) {
+  if (!coef_rows) return IAS_ERR_ARG;
+  return grad_frames_launch<true>(audio, tables, nullptr, nullptr, nullptr, nullptr, 0, n_out, target, coef_rows,
+                                  frame_grad, B, T, n_fft, hop, 1, 2, 0.0f, eps, nullptr, (hipStream_t)stream_);
+}
+
+extern "C" int ias_stft_grad_spans_mrstft_rows(const float* audio, const float* tables, int n_out, const float* target,
+                                               const double* coef_rows, float* chunk_spans, int B, int T, int n_fft,
+                                               int hop, float eps, int* plan_host, void* stream_) {
+  if (!coef_rows || !plan_host || (reinterpret_cast<uintptr_t>(chunk_spans) & 15) != 0) return IAS_ERR_ARG;
+  return grad_frames_launch<true>(audio, tables, nullptr, nullptr, nullptr, nullptr, 0, n_out, target, coef_rows,
+                                  chunk_spans, B, T, n_fft, hop, 1, 2, 0.0f, eps, plan_host, (hipStream_t)stream_);
 }
 
 // sums[0..2] = sum over n partial triples (fixed order: deterministic); optionally

@@ -182,8 +182,9 @@ class AudioToParams(nn.Module):
 
     def match(self, audio, steps=200, **kw):
         """Sound matching (match.SoundMatcher) started from the MLP's prediction: audio [N, T] at this module's voice
-        rate and length -> match.MatchResult.  ``kw``: SoundMatcher's arguments (loss, lr, betas, eps, frozen; the mel
-        settings default to cfg.mel) and ``return_audio``."""
+        rate and length -> match.MatchResult.  ``kw``: SoundMatcher's arguments (loss: "mel_l1", "stft_l1" or
+        "multi_resolution_stft"; mel_kwargs, stft_kwargs, mrstft_kwargs, lr, betas, eps, frozen; the mel settings default
+        to cfg.mel) and ``return_audio``."""
         from .match import SoundMatcher
         return_audio = kw.pop("return_audio", False)
         kw.setdefault("mel_kwargs", dict(self.cfg.mel))

@@ -7,8 +7,9 @@ mel-L1 against the true audio) as a product feature, and returns what its notebo
 Per chunk of ``voice.batch_size`` targets, every iteration is
 
     audio = voice.render(p)                      HIP render with its adjoint (voice_grad.py), normalize=True
-    L     = loss.per_item(audio, target)         [B] per-sound spectral L1 (spectral.py, csrc/match_kernels.hip)
-    L.backward(active)                           per-row cotangent (ias_stft_loss_backward_rows): a sound's gradient
+    L     = loss.per_item(audio, target)         [B] per-sound spectral L1 or MR-STFT (spectral.py, csrc/match_kernels.hip)
+    L.backward(active)                           per-row cotangent (ias_stft_loss_backward_rows, ias_mrstft_coef_rows +
+                                                 the *_mrstft_rows span / frame kernels): a sound's gradient
                                                  does not depend on the batch, padded rows get exactly 0
     ias_match_adam_step                          best-so-far, non-finite skip, Adam per row, clamp to [0, 1]
 
@@ -21,7 +22,9 @@ import torch
 
 from . import _lib
 from . import voice_spec as S
-from .spectral import MelSpectrogramL1, STFTL1
+from .spectral import MelSpectrogramL1, MultiResolutionSTFTLoss, STFTL1
+
+LOSSES = ("mel_l1", "stft_l1", "multi_resolution_stft")
 
 
 @dataclass
@@ -54,12 +57,14 @@ def match_adam_step(params01, grad, m, v, step, loss, best_loss, best_params, fr
 class SoundMatcher:
     """Fit Voice parameters to target sounds by descent through the HIP render and a per-sound spectral loss.
 
-    ``loss``: "mel_l1" (``MelSpectrogramL1(sample_rate=voice rate, **mel_kwargs)``) or "stft_l1" (``STFTL1(**stft_kwargs)``).
+    ``loss``: "mel_l1" (``MelSpectrogramL1(sample_rate=voice rate, **mel_kwargs)``), "stft_l1" (``STFTL1(**stft_kwargs)``)
+    or "multi_resolution_stft" (``MultiResolutionSTFTLoss(**mrstft_kwargs)``: auraloss' defaults, FFT sizes 1024 / 2048 /
+    512, hops 120 / 240 / 50, windows 600 / 1200 / 240, when none are given).
     ``frozen``: keys as ``Voice.get_parameters()`` ((module, name) pairs) that keep their initial value.  The matcher
     renders with explicit parameters: it leaves ``voice.params01`` and the voice's own frozen set alone."""
 
     def __init__(self, voice, loss="mel_l1", mel_kwargs=None, stft_kwargs=None, lr=0.01, betas=(0.9, 0.999), eps=1e-8,
-                 frozen=()):
+                 frozen=(), mrstft_kwargs=None):
         self.voice = voice
         if loss == "mel_l1":
             kw = dict(mel_kwargs or {})
@@ -67,8 +72,10 @@ class SoundMatcher:
             self.loss = MelSpectrogramL1(**kw)
         elif loss == "stft_l1":
             self.loss = STFTL1(**dict(stft_kwargs or {}))
+        elif loss == "multi_resolution_stft":
+            self.loss = MultiResolutionSTFTLoss(**dict(mrstft_kwargs or {}))
         else:
-            raise ValueError(f"unknown matching loss {loss!r}: 'mel_l1' or 'stft_l1'")
+            raise ValueError(f"unknown matching loss {loss!r}: " + ", ".join(repr(n) for n in LOSSES))
         self.loss_kind = loss
         self.loss.to(voice.params01.device)
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
@@ -82,6 +89,8 @@ class SoundMatcher:
     def _per_item(self, audio, target):
         if self.loss_kind == "mel_l1":
             return self.loss.per_item(audio, target_mel=target)
+        if self.loss_kind == "multi_resolution_stft":
+            return self.loss.per_item(audio, targets=target)
         return self.loss.per_item(audio, target_values=target)
 
     def fit(self, target_audio, init_params01=None, steps=200, return_audio=False):

@@ -212,6 +212,23 @@ class STFTPlan(nn.Module):
                                    _lib.stream()), "ias_l1_rows")
         return out
 
+    def mrstft_rows(self, values, target_values):
+        """Per-row MR-STFT sums of one resolution: two [B, frames, n_out] tensors of clamped magnitudes -> [B, 3] fp64
+        {sum (T - V)^2, sum T^2, sum |ln V - ln T|} (ias_mrstft_rows: fixed order, a row's sums the same bits wherever it
+        sits in the batch)."""
+        lib = _lib.load()
+        assert values.shape == target_values.shape and values.is_contiguous() and target_values.is_contiguous()
+        _lib.require_f32(values, target_values)
+        B = values.shape[0]
+        n = values[0].numel()
+        nch = lib.ias_mrstft_rows_partials_count(n)
+        _lib.check(min(nch, 0), "ias_mrstft_rows_partials_count")
+        partials = torch.empty((B, nch, 3), dtype=torch.float64, device=values.device)
+        sums = torch.empty((B, 3), dtype=torch.float64, device=values.device)
+        _lib.check(lib.ias_mrstft_rows(_lib.ptr(values), _lib.ptr(target_values), B, n, _lib.ptr(partials), _lib.ptr(sums),
+                                       _lib.stream()), "ias_mrstft_rows")
+        return sums
+
 
 class _L1LossFn(torch.autograd.Function):
     """mean |V(audio) - target| with the fused HIP forward and the HIP adjoint w.r.t. the audio."""
@@ -397,6 +414,18 @@ class MultiResolutionSTFTLoss(nn.Module):
             return _MRSTFTFn.apply(x, self, *targets)
         return self._forward(x, targets)[0]
 
+    def per_item(self, x, y=None, targets=None):
+        """[B] fp32: the loss of each sound on its own (``forward`` applied to row b alone; at B = 1 the same value up to
+        the order of summation), differentiable w.r.t. ``x``.  A row's value and gradient do not depend on its position
+        in the batch or on the other rows (same bits).  The target as for ``forward``."""
+        assert (y is None) != (targets is None), "give the target audio or its cached magnitudes"
+        if targets is None:
+            targets = self.target(y)
+        targets = [t.detach().contiguous() for t in targets]
+        if torch.is_grad_enabled() and x.requires_grad:
+            return _MRSTFTRowsFn.apply(x, self, *targets)
+        return self._forward_rows(STFTPlan._audio2d(x), targets)[0]
+
     def _streams(self, device):
         """One side stream per resolution (created once per device).  The kernels of the three resolutions are latency
         bound at low occupancy and independent of each other: issued on three streams they overlap (forward and backward
@@ -431,6 +460,34 @@ class MultiResolutionSTFTLoss(nn.Module):
         counts = (ctypes.c_double * n)(*[float(t.numel()) for t in targets])
         _lib.check(_lib.load().ias_mrstft_total(ptrs, counts, n, _lib.ptr(loss), _lib.stream()), "ias_mrstft_total")
         return loss, saved
+
+    def _forward_rows(self, a, targets):
+        """Per resolution the values pass and ias_mrstft_rows (on the side streams when ``parallel``), then one
+        ias_mrstft_rows_total on the caller's stream -> ([B] fp32, [B, 3] fp64 sums per resolution)."""
+        B = a.shape[0]
+        cur = torch.cuda.current_stream(a.device)
+        streams = self._streams(a.device) if self.parallel else None
+        sums = []
+        for k, (plan, tgt) in enumerate(zip(self.plans, targets)):
+            assert tgt.shape == (B, plan.num_frames(a.shape[1]), plan.n_out)
+            if streams is None:
+                sums.append(plan.mrstft_rows(plan.values(a, VALUE_MAG_CLAMPED, self.eps), tgt))
+            else:
+                streams[k].wait_stream(cur)
+                with torch.cuda.stream(streams[k]):
+                    s = plan.mrstft_rows(plan.values(a, VALUE_MAG_CLAMPED, self.eps), tgt)
+                    s.record_stream(cur)
+                    sums.append(s)
+        if streams is not None:
+            for st in streams[:len(sums)]:
+                cur.wait_stream(st)
+        n = len(sums)
+        out = torch.empty(B, dtype=torch.float32, device=a.device)
+        ptrs = (ctypes.c_void_p * n)(*[s.data_ptr() for s in sums])
+        counts = (ctypes.c_double * n)(*[float(t[0].numel()) for t in targets])
+        _lib.check(_lib.load().ias_mrstft_rows_total(ptrs, counts, n, B, _lib.ptr(out), _lib.stream()),
+                   "ias_mrstft_rows_total")
+        return out, sums
 
 
 class _MRSTFTFn(torch.autograd.Function):
@@ -494,6 +551,83 @@ class _MRSTFTFn(torch.autograd.Function):
                 cur.wait_stream(streams[i])
             g_total = g_audio if g_total is None else g_total + g_audio
         return (g_total.reshape(ctx.shape), None) + (None,) * len(module.plans)
+
+
+class _MRSTFTRowsFn(torch.autograd.Function):
+    """MultiResolutionSTFTLoss.per_item with the HIP adjoint w.r.t. the prediction for a cotangent per row: per resolution
+    the coefficient pairs of every row (ias_mrstft_coef_rows, the row's cotangent folded in), then the span kernels with one
+    ias_stft_grad_combine for all resolutions, or, where a resolution's shape has no span plan, the per-resolution path
+    summed in resolution order (as _MRSTFTFn.backward)."""
+
+    @staticmethod
+    def forward(ctx, x, module, *targets):
+        a = STFTPlan._audio2d(x)
+        out, sums = module._forward_rows(a, targets)
+        ctx.module, ctx.shape = module, x.shape
+        ctx.save_for_backward(a, *targets, *sums)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_rows):
+        module = ctx.module
+        nres = len(module.plans)
+        a, rest = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        targets, sums = rest[:nres], rest[nres:]
+        lib = _lib.load()
+        B, T = a.shape
+        g = g_rows.to(torch.float32).reshape(B).contiguous()
+        cur = torch.cuda.current_stream(a.device)
+        streams = module._streams(a.device) if module.parallel else None
+        eps = float(module.eps)
+        plans = []
+        for plan in module.plans:
+            hp = (ctypes.c_int * 3)()
+            if lib.ias_stft_grad_span_plan(B, T, plan.n_fft, plan.hop_length, 0, plan.n_out, hp) == 0:
+                plans.append((hp[0], hp[1], hp[2]))
+        spans_path = len(plans) == nres and nres <= 8
+        parts = []
+        for i, plan in enumerate(module.plans):
+            if streams is not None:
+                streams[i].wait_stream(cur)
+            with torch.cuda.stream(streams[i] if streams is not None else cur):
+                side = torch.cuda.current_stream(a.device)
+                g.record_stream(side)
+                coef = torch.empty((B, 2), dtype=torch.float64, device=a.device)
+                _lib.check(lib.ias_mrstft_coef_rows(_lib.ptr(sums[i]), _lib.ptr(g), float(targets[i][0].numel()), nres, B,
+                                                    _lib.ptr(coef), _lib.stream()), "ias_mrstft_coef_rows")
+                if spans_path:
+                    G, cper, L = plans[i]
+                    out = torch.empty(B * cper * L, dtype=torch.float32, device=a.device)
+                    hp = (ctypes.c_int * 3)()
+                    _lib.check(lib.ias_stft_grad_spans_mrstft_rows(
+                        _lib.ptr(a), _lib.ptr(plan.tables), plan.n_out, _lib.ptr(targets[i]), _lib.ptr(coef), _lib.ptr(out),
+                        B, T, plan.n_fft, plan.hop_length, eps, hp, _lib.stream()), "ias_stft_grad_spans_mrstft_rows")
+                    assert (hp[0], hp[1], hp[2]) == plans[i]
+                else:
+                    frame_grad = torch.empty((B, plan.num_frames(T), plan.n_fft), dtype=torch.float32, device=a.device)
+                    out = torch.empty_like(a)
+                    _lib.check(lib.ias_stft_loss_backward_mrstft_rows(
+                        _lib.ptr(a), _lib.ptr(plan.window), _lib.ptr(plan.tables), _lib.ptr(targets[i]), _lib.ptr(coef),
+                        _lib.ptr(frame_grad), _lib.ptr(out), B, T, plan.n_fft, plan.hop_length, plan.n_out, eps,
+                        _lib.stream()), "ias_stft_loss_backward_mrstft_rows")
+                out.record_stream(cur)
+                parts.append(out)
+        if streams is not None:
+            for st in streams[:nres]:
+                cur.wait_stream(st)
+        if spans_path:
+            g_total = torch.empty_like(a)
+            ptrs = (ctypes.c_void_p * nres)(*[sp.data_ptr() for sp in parts])
+            flat = []
+            for plan, (G, cper, L) in zip(module.plans, plans):
+                flat += [plan.n_fft, plan.hop_length, G, cper, L]
+            _lib.check(lib.ias_stft_grad_combine(ptrs, (ctypes.c_int * len(flat))(*flat), nres, None, _lib.ptr(g_total),
+                                                 B, T, _lib.stream()), "ias_stft_grad_combine")
+        else:
+            g_total = parts[0]
+            for p in parts[1:]:                  # joined in a fixed order
+                g_total = g_total + p
+        return (g_total.reshape(ctx.shape), None) + (None,) * nres
 
 
 def _mrstft_coef(lib, s, g32, count, nres, device):

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Sound matching entry point: fit the 78 Voice parameters to WAV files.
 
-    python match_audio.py in1.wav in2.wav --steps 200 --out DIR [--init center|random] [key=value ...]
+    python match_audio.py in1.wav in2.wav --steps 200 --out DIR [--init center|random] [--loss LOSS] [key=value ...]
 
 ``key=value`` are config overrides as for pretrain.py / audio_to_params.py (``torchsynth.rate``,
 ``torchsynth.buffer_size_seconds``, ``mel.*``); the matcher's own settings are flags.  Input WAVs are 16- or 32-bit
 integer PCM at ``torchsynth.rate`` (no resampling); several channels are averaged; a file longer or shorter than the
 synth buffer is cropped or zero-padded, with a warning.  Per input NAME the script writes NAME.params.json (every
-parameter in 0..1 and in its own units, the initial and final loss) and NAME.match.wav (the best render, 16-bit PCM)."""
+parameter in 0..1 and in its own units, the loss, its initial and final value) and NAME.match.wav (the best render,
+16-bit PCM).  ``--loss``: mel_l1 (the ``mel.*`` settings), stft_l1 or multi_resolution_stft (auraloss' three resolutions,
+whose 1.1 ms hop constrains the envelopes' short segments better)."""
 import argparse
 import json
 import os
@@ -77,7 +79,7 @@ def main(argv=None):
     ap.add_argument("--out", required=True, help="output directory")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--init", choices=("center", "random"), default="center")
-    ap.add_argument("--loss", choices=("mel_l1", "stft_l1"), default="mel_l1")
+    ap.add_argument("--loss", choices=("mel_l1", "stft_l1", "multi_resolution_stft"), default="mel_l1")
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--beta1", type=float, default=0.9)
     ap.add_argument("--beta2", type=float, default=0.999)
