@@ -366,6 +366,20 @@ int ias_stft_grad_spans_mrstft_rows(const float* audio, const float* tables, int
                                     const double* coef_rows, float* chunk_spans, int B, int T, int n_fft, int hop,
                                     float eps, int* plan_host, void* stream);
 
+/* ---- Spectral bank (retrieval.SpectralBank): start sound matching from the nearest bank voices.
+ * The reference's nearest-candidate search (/root/reference/evaluate_audio_representations.py:202-231) under the loss
+ * of its parameter fit (/root/reference/audio_to_params.py:56-172).
+ * ias_l1_cdist: dist[n*M + m] (device fp32 [N, M]) = sum_k |queries[n,k] - bank[m,k]| / K; queries [N, K], bank [M, K]
+ *   row-major fp32 (row stride K); N, M, K >= 1.  workspace: device, ias_l1_cdist_workspace_bytes(N, M, K) bytes (< 0 on
+ *   bad arguments).  Same per-row contract as ias_l1_rows: K is cut into 4096-element chunks from the rows' start, a chunk
+ *   is added in fp32 in a fixed order (32-element slices in k order, the slice sums in slice order), the chunk sums are
+ *   folded in fp64 in chunk order, divided by K and rounded once.  dist[n,m] is the same bits for the same two rows
+ *   whatever N, M, n, m or the rows' addresses (any 4-byte alignment).  NaN / Inf in a row are not sanitised: they make
+ *   that distance non-finite. */
+long long ias_l1_cdist_workspace_bytes(int N, int M, long long K);
+int ias_l1_cdist(const float* queries, const float* bank, int N, int M, long long K, void* workspace, float* dist,
+                 void* stream);
+
 /* sums[3] (doubles) = column sums of partials [n][3], fixed order (deterministic); when mean_out is not
  * NULL also mean_out[0] = (float)(sums[0] * scale). */
 int ias_reduce_partials(const double* partials, long long n, double* sums, double scale, float* mean_out,

@@ -1,0 +1,178 @@
+// Spectral bank (MI355X / gfx950): the all-pairs L1 distance between target spectrograms and the spectrograms of a bank
+// of rendered voices (inverse-audio-synthesis_amd/retrieval.py: SpectralBank), the hot part of starting sound matching
+// from the nearest voices.  The reference searches the closest candidate of each test sound with torch.cdist
+// (/root/reference/evaluate_audio_representations.py:202-231) and fits parameters through mel-L1
+// (/root/reference/audio_to_params.py:56-172); here the distance is the matcher's own per-sound loss.
+//
+// dist[n, m] = sum_k |q[n, k] - b[m, k]| / K.  L1 is not a product, so neither the matrix cores nor a GEMM library apply:
+// a tiled VALU kernel.
+//
+// Summation order (the per-row contract of ias_l1_rows): K is cut into chunks of CD_CHUNK = 4096 elements from the row's
+// start, a chunk into slices of CD_KS = 32.  A slice's 32 terms are added in fp32 in k order starting from 0, the slice
+// sums of a chunk are added in fp32 in slice order, the chunk sums are folded in fp64 in chunk order, divided by K in fp64
+// and rounded to fp32 once.  Elements past K are loaded as 0 for both operands: |0 - 0| = +0 leaves every sum as it is.
+// Nothing in that order depends on N, M, n, m, the tile shape, the grid or where the rows sit in memory (the operands are
+// read element by element), so a pair's distance is the same bits in every launch.
+//
+// l1_cdist_chunks_kernel<R, C, TY, TX>: grid (M tiles, N tiles, chunks), TY x TX lanes; lane (ty, tx) owns the R x C
+//   pairs (n0 + ty R + i, m0 + tx C + j).  Per slice both operand tiles are staged in LDS k-major ([k][row]), so a lane
+//   reads its R queries and C bank values of one k with ds_read_b128 (R, C multiples of 4; or 1) and spends one
+//   v_sub_f32 and one v_add_f32 with an |.| source modifier per (pair, k).  The next slice is loaded into registers
+//   while the current one is reduced.  The chunk's fp64 sum goes to ws[chunk][n][m].
+// l1_cdist_fold_kernel: one lane per pair adds its chunk sums in chunk order.
+#include "ias_common.h"
+#include <cstdint>
+
+#define CD_CHUNK 4096
+#define CD_KS 32
+#define CD_PAD 4
+
+template <int R, int C, int TY, int TX>
+__global__ __launch_bounds__(TY * TX) void l1_cdist_chunks_kernel(const float* __restrict__ q,
+                                                                     const float* __restrict__ b, int N, int M,
+                                                                     long long K, double* __restrict__ ws) {
+  constexpr int CD_THREADS = TY * TX;
+  static_assert((R % 4 == 0 || R == 1) && (C % 4 == 0 || C == 1), "micro-tile");
+  constexpr int TN = R * TY, TM = C * TX;
+  constexpr int LQ = TN + CD_PAD, LB = TM + CD_PAD;              // LDS row strides (floats), 16-byte multiples
+  constexpr int RS = CD_THREADS / CD_KS;                        // operand rows staged per load pass
+  static_assert(CD_THREADS % CD_KS == 0 && TN % RS == 0 && TM % RS == 0, "staging");
+  constexpr int NQ = TN / RS, NB = TM / RS;
+  __shared__ __attribute__((aligned(16))) float s_q[CD_KS * LQ];
+  __shared__ __attribute__((aligned(16))) float s_b[CD_KS * LB];
+
+  const int tid = threadIdx.x, tx = tid % TX, ty = tid / TX;
+  const int m0 = blockIdx.x * TM, n0 = blockIdx.y * TN;
+  const long long k0 = (long long)blockIdx.z * CD_CHUNK;
+  const long long klen = K - k0 < CD_CHUNK ? K - k0 : CD_CHUNK;
+  const int nslices = (int)((klen + CD_KS - 1) / CD_KS);
+
+  // staging: lane tid loads element k0 + s CD_KS + kk of rows r0 + u RS of the Q and B tiles (consecutive lanes read
+  // consecutive k of one row); rows past N or M and elements past K are 0.  Only valid addresses are dereferenced.
+  const int kk_ld = tid % CD_KS, r0 = tid / CD_KS;
+  const size_t rstride = (size_t)RS * K;
+  const float* qp = q + (size_t)(n0 + r0) * K + k0 + kk_ld;
+  const float* bp = b + (size_t)(m0 + r0) * K + k0 + kk_ld;
+  float pq[NQ], pb[NB];
+  auto fetch = [&](int s) {
+    const long long ko = (long long)s * CD_KS;
+    const bool kin = kk_ld + ko < klen;
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) pq[u] = (kin && n0 + r0 + u * RS < N) ? qp[u * rstride + ko] : 0.0f;
+#pragma unroll
+    for (int u = 0; u < NB; ++u) pb[u] = (kin && m0 + r0 + u * RS < M) ? bp[u * rstride + ko] : 0.0f;
+  };
+  auto stage = [&]() {
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) s_q[kk_ld * LQ + r0 + u * RS] = pq[u];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) s_b[kk_ld * LB + r0 + u * RS] = pb[u];
+  };
+
+  float acc[R][C];
+#pragma unroll
+  for (int i = 0; i < R; ++i)
+#pragma unroll
+    for (int j = 0; j < C; ++j) acc[i][j] = 0.0f;
+
+  fetch(0);
+  for (int s = 0; s < nslices; ++s) {
+    __syncthreads();                                   // the previous slice's readers are done with the LDS tiles
+    stage();
+    __syncthreads();
+    if (s + 1 < nslices) fetch(s + 1);
+    float part[R][C];
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+      for (int j = 0; j < C; ++j) part[i][j] = 0.0f;
+#pragma unroll
+    for (int kk = 0; kk < CD_KS; ++kk) {
+      float a[R], c[C];
+      if constexpr (R == 1) {
+        a[0] = s_q[kk * LQ + ty];
+      } else {
+#pragma unroll
+        for (int i = 0; i < R; i += 4) {
+          const float4 v = *reinterpret_cast<const float4*>(&s_q[kk * LQ + ty * R + i]);
+          a[i] = v.x; a[i + 1] = v.y; a[i + 2] = v.z; a[i + 3] = v.w;
+        }
+      }
+      if constexpr (C == 1) {
+        c[0] = s_b[kk * LB + tx];
+      } else {
+#pragma unroll
+        for (int j = 0; j < C; j += 4) {
+          const float4 v = *reinterpret_cast<const float4*>(&s_b[kk * LB + tx * C + j]);
+          c[j] = v.x; c[j + 1] = v.y; c[j + 2] = v.z; c[j + 3] = v.w;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < R; ++i)
+#pragma unroll
+        for (int j = 0; j < C; ++j) part[i][j] += fabsf(a[i] - c[j]);
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+      for (int j = 0; j < C; ++j) acc[i][j] += part[i][j];
+  }
+
+  double* out = ws + (size_t)blockIdx.z * N * M;
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const int n = n0 + ty * R + i;
+    if (n >= N) continue;
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+      const int m = m0 + tx * C + j;
+      if (m < M) out[(size_t)n * M + m] = (double)acc[i][j];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void l1_cdist_fold_kernel(const double* __restrict__ ws, long long NM, int nchunks,
+                                                           double K, float* __restrict__ dist) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= NM) return;
+  double s = ws[p];
+  for (int c = 1; c < nchunks; ++c) s += ws[(size_t)c * NM + p];
+  dist[p] = (float)(s / K);
+}
+
+template <int R, int C, int TY, int TX>
+static void launch_chunks(const float* q, const float* b, int N, int M, long long K, int nchunks, double* ws,
+                          hipStream_t stream) {
+  constexpr int TN = R * TY, TM = C * TX;
+  hipLaunchKernelGGL((l1_cdist_chunks_kernel<R, C, TY, TX>), dim3((M + TM - 1) / TM, (N + TN - 1) / TN, nchunks),
+                     dim3(TY * TX), 0, stream, q, b, N, M, K, ws);
+}
+
+// ------------------------------------------------------------------------------------------------ C ABI
+static long long cdist_nchunks(long long K) { return (K + CD_CHUNK - 1) / CD_CHUNK; }
+
+extern "C" long long ias_l1_cdist_workspace_bytes(int N, int M, long long K) {
+  if (N <= 0 || M <= 0 || K <= 0) return IAS_ERR_ARG;
+  const long long nch = cdist_nchunks(K);
+  if (nch > 65535) return IAS_ERR_ARG;                  // grid z
+  const long long nm = (long long)N * M;
+  if (nm > (1LL << 40) / (8 * nch)) return IAS_ERR_ARG;
+  return nm * nch * 8;
+}
+
+extern "C" int ias_l1_cdist(const float* queries, const float* bank, int N, int M, long long K, void* workspace,
+                            float* dist, void* stream_) {
+  if (!queries || !bank || !workspace || !dist) return IAS_ERR_ARG;
+  if (ias_l1_cdist_workspace_bytes(N, M, K) < 0) return IAS_ERR_ARG;
+  const int nchunks = (int)cdist_nchunks(K);
+  hipStream_t stream = (hipStream_t)stream_;
+  double* ws = (double*)workspace;
+  // The tile shape only changes how much work a launch wastes on padding, never a result (see the summation order).
+  if (N <= 4) launch_chunks<4, 1, 1, 64>(queries, bank, N, M, K, nchunks, ws, stream);
+  else if (N <= 32) launch_chunks<4, 4, 8, 32>(queries, bank, N, M, K, nchunks, ws, stream);
+  else launch_chunks<8, 4, 16, 16>(queries, bank, N, M, K, nchunks, ws, stream);
+  const long long NM = (long long)N * M;
+  hipLaunchKernelGGL(l1_cdist_fold_kernel, dim3((unsigned)((NM + 255) / 256)), dim3(256), 0, stream, ws, NM, nchunks,
+                     (double)K, dist);
+  return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
+}

@@ -34,6 +34,9 @@ class MatchResult:
     initial_loss: torch.Tensor      # [N] fp32: the loss of the initial parameters
     skipped: torch.Tensor           # [N] int32: iterations skipped for a non-finite loss or gradient
     audio: Optional[torch.Tensor] = None   # [N, T] render of params01 (fit(return_audio=True))
+    start: Optional[torch.Tensor] = None   # [N] int64: the chosen start (init_params01 [N, S, 78] only)
+    start_loss: Optional[torch.Tensor] = None            # [N, S] fp32: each start's final loss
+    start_initial_loss: Optional[torch.Tensor] = None    # [N, S] fp32: each start's initial loss
 
 
 def match_adam_step(params01, grad, m, v, step, loss, best_loss, best_params, free, active, skipped, lr, betas, eps):
@@ -96,17 +99,33 @@ class SoundMatcher:
     def fit(self, target_audio, init_params01=None, steps=200, return_audio=False):
         """target_audio [N, T] (device, T == voice.synthconfig.buffer_size); init_params01 [N, 78] in 0..1 (None: 0.5)
         -> ``MatchResult``.  Targets go through in chunks of ``voice.batch_size``; the last chunk is padded with inactive
-        rows (zero cotangent, never updated, not returned)."""
+        rows (zero cotangent, never updated, not returned).
+
+        Several starts per sound: init_params01 [N, S, 78].  The N S rows are fitted as one flattened [N S, 78] fit
+        (row n S + s fits target n from start s) and, per sound, the start with the lowest final loss is kept (ties: the
+        lowest s; ``retrieval.rank_distances``).  ``loss``, ``initial_loss``, ``skipped`` and ``audio`` are the chosen
+        start's; ``start``, ``start_loss`` and ``start_initial_loss`` say which and how every start ended."""
         voice = self.voice
-        B, T = voice.batch_size, voice.synthconfig.buffer_size
+        T = voice.synthconfig.buffer_size
         dev = voice.params01.device
         if target_audio.dim() != 2 or target_audio.shape[1] != T:
             raise ValueError(f"target_audio must be [N, {T}] (the voice's buffer), got {tuple(target_audio.shape)}")
         N = target_audio.shape[0]
+        if init_params01 is not None and init_params01.dim() == 3:
+            if init_params01.shape[0] != N or init_params01.shape[2] != S.NPARAMS or init_params01.shape[1] < 1:
+                raise ValueError(f"init_params01 must be [{N}, {S.NPARAMS}] or [{N}, starts, {S.NPARAMS}], got "
+                                 f"{tuple(init_params01.shape)}")
+            return self._fit_starts(target_audio, init_params01, steps, return_audio)
         if init_params01 is None:
             init_params01 = torch.full((N, S.NPARAMS), 0.5, dtype=torch.float32, device=dev)
         if tuple(init_params01.shape) != (N, S.NPARAMS):
             raise ValueError(f"init_params01 must be [{N}, {S.NPARAMS}], got {tuple(init_params01.shape)}")
+        return self._fit_rows(target_audio, init_params01, steps, return_audio)
+
+    def _fit_rows(self, target_audio, init_params01, steps, return_audio):
+        voice = self.voice
+        B, dev = voice.batch_size, voice.params01.device
+        N = target_audio.shape[0]
         target_audio = target_audio.detach().to(device=dev, dtype=torch.float32)
         init_params01 = init_params01.detach().to(device=dev, dtype=torch.float32).clamp(0.0, 1.0)
         outs = [self._fit_chunk(target_audio[s:s + B], init_params01[s:s + B], int(steps), return_audio)
@@ -114,6 +133,19 @@ class SoundMatcher:
         cat = lambda i: torch.cat([o[i] for o in outs])     # noqa: E731
         return MatchResult(params01=cat(0), loss=cat(1), initial_loss=cat(2), skipped=cat(3),
                            audio=cat(4) if return_audio else None)
+
+    def _fit_starts(self, target_audio, init_params01, steps, return_audio):
+        from .retrieval import rank_distances
+        N, nS = init_params01.shape[0], init_params01.shape[1]
+        flat = self._fit_rows(target_audio.repeat_interleave(nS, dim=0), init_params01.reshape(N * nS, S.NPARAMS),
+                              steps, return_audio)
+        start_loss = flat.loss.reshape(N, nS)
+        start = rank_distances(start_loss)[:, 0]
+        rows = torch.arange(N, device=start.device) * nS + start
+        pick = lambda t: None if t is None else t[rows]      # noqa: E731
+        return MatchResult(params01=pick(flat.params01), loss=pick(flat.loss), initial_loss=pick(flat.initial_loss),
+                           skipped=pick(flat.skipped), audio=pick(flat.audio), start=start, start_loss=start_loss,
+                           start_initial_loss=flat.initial_loss.reshape(N, nS))
 
     def _fit_chunk(self, target, init, steps, return_audio):
         voice = self.voice

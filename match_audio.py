@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Sound matching entry point: fit the 78 Voice parameters to WAV files.
 
-    python match_audio.py in1.wav in2.wav --steps 200 --out DIR [--init center|random] [--loss LOSS] [key=value ...]
+    python match_audio.py in1.wav in2.wav --steps 200 --out DIR [--init center|random|bank] [--starts S]
+                          [--bank-batches NB] [--loss LOSS] [key=value ...]
 
 ``key=value`` are config overrides as for pretrain.py / audio_to_params.py (``torchsynth.rate``,
 ``torchsynth.buffer_size_seconds``, ``mel.*``); the matcher's own settings are flags.  Input WAVs are 16- or 32-bit
@@ -9,7 +10,10 @@ integer PCM at ``torchsynth.rate`` (no resampling); several channels are average
 synth buffer is cropped or zero-padded, with a warning.  Per input NAME the script writes NAME.params.json (every
 parameter in 0..1 and in its own units, the loss, its initial and final value) and NAME.match.wav (the best render,
 16-bit PCM).  ``--loss``: mel_l1 (the ``mel.*`` settings), stft_l1 or multi_resolution_stft (auraloss' three resolutions,
-whose 1.1 ms hop constrains the envelopes' short segments better)."""
+whose 1.1 ms hop constrains the envelopes' short segments better).  ``--init``: center (every parameter 0.5), random
+(``--starts`` draws per sound) or bank: a ``retrieval.SpectralBank`` of ``--bank-batches`` x 128 random voices is rendered
+and each sound starts from its ``--starts`` nearest voices under the matcher's loss (a mel bank for
+multi_resolution_stft); the best start is kept and the JSON record names it (``bank_index``, ``bank_distance``)."""
 import argparse
 import json
 import os
@@ -73,12 +77,19 @@ def params_record(params01_row):
             for i, (m, n, *_r) in enumerate(S.PARAMS)]
 
 
-def main(argv=None):
+INITS = ("center", "random", "bank")
+BANK_BATCH = 128
+
+
+def parse_args(argv=None):
+    """The command line -> (args, WAV files, config overrides); refusals exit through ``argparse`` (SystemExit 2)."""
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("inputs", nargs="+", help="WAV files (16/32-bit PCM) and key=value config overrides")
     ap.add_argument("--out", required=True, help="output directory")
     ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--init", choices=("center", "random"), default="center")
+    ap.add_argument("--init", choices=INITS, default="center")
+    ap.add_argument("--starts", type=int, default=1, help="starts per sound (--init random or bank; center: 1)")
+    ap.add_argument("--bank-batches", type=int, default=32, help="--init bank: voice batches of 128 in the bank")
     ap.add_argument("--loss", choices=("mel_l1", "stft_l1", "multi_resolution_stft"), default="mel_l1")
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--beta1", type=float, default=0.9)
@@ -91,6 +102,17 @@ def main(argv=None):
     overrides = [a for a in args.inputs if "=" in a]
     if not files:
         ap.error("no input WAV files")
+    if args.starts < 1:
+        ap.error("--starts must be >= 1")
+    if args.init == "center" and args.starts != 1:
+        ap.error("--init center has one start per sound: --starts must be 1")
+    if args.bank_batches < 1:
+        ap.error("--bank-batches must be >= 1")
+    return args, files, overrides
+
+
+def main(argv=None):
+    args, files, overrides = parse_args(argv)
 
     import torch
     from inverse_audio_synthesis_amd.config import load_config
@@ -99,7 +121,7 @@ def main(argv=None):
     cfg = load_config(os.path.join(ROOT, "conf"), "config", overrides)
     rate = int(cfg.torchsynth.rate)
     dev = torch.device("cuda:0")
-    batch = max(1, min(len(files), int(args.batch_size)))
+    batch = max(1, min(len(files) * args.starts, int(args.batch_size)))
     voice = Voice(SynthConfig(batch_size=batch, sample_rate=rate, buffer_size_seconds=cfg.torchsynth.buffer_size_seconds,
                               reproducible=cfg.torchsynth.reproducible)).to(dev)
     T = voice.synthconfig.buffer_size
@@ -108,12 +130,35 @@ def main(argv=None):
     except ValueError as e:
         sys.exit(f"match_audio.py: {e}")
     target = torch.from_numpy(target).to(dev)
-    if args.init == "random":
-        init = torch.rand((len(files), 78), generator=torch.Generator().manual_seed(args.seed)).to(dev)
-    else:
-        init = None
     matcher = SoundMatcher(voice, loss=args.loss, mel_kwargs=dict(cfg.mel), lr=args.lr, betas=(args.beta1, args.beta2),
                            eps=args.eps)
+    N, nS = len(files), args.starts
+    bank_idx = bank_dist = None
+    if args.init == "random":
+        init = torch.rand((N * nS, 78), generator=torch.Generator().manual_seed(args.seed)).to(dev)
+        init = init.reshape(N, nS, 78) if nS > 1 else init
+    elif args.init == "bank":
+        from inverse_audio_synthesis_amd.retrieval import SpectralBank
+        from inverse_audio_synthesis_amd.spectral import MelSpectrogramL1
+        bank_voice = Voice(SynthConfig(batch_size=BANK_BATCH, sample_rate=rate,
+                                       buffer_size_seconds=cfg.torchsynth.buffer_size_seconds,
+                                       reproducible=cfg.torchsynth.reproducible)).to(dev)
+        if args.loss == "multi_resolution_stft":
+            kw = dict(cfg.mel)
+            kw.setdefault("sample_rate", rate)
+            bank_loss = MelSpectrogramL1(**kw).to(dev)
+        else:
+            bank_loss = matcher.loss
+        nbytes = SpectralBank.nbytes(bank_voice, bank_loss, args.bank_batches)
+        print(f"match_audio.py: building a spectral bank of {args.bank_batches * BANK_BATCH} voices "
+              f"({nbytes} bytes)", flush=True)
+        bank = SpectralBank(bank_voice, bank_loss, range(args.bank_batches))
+        bank_dist, bank_idx = bank.nearest(target_audio=target, k=nS)
+        nS = bank_idx.shape[1]
+        init = bank.params01[bank_idx.reshape(-1)].reshape(N, nS, 78)
+        del bank
+    else:
+        init = None
     res = matcher.fit(target, init_params01=init, steps=args.steps, return_audio=True)
     os.makedirs(args.out, exist_ok=True)
     audio = res.audio.cpu().numpy()
@@ -121,7 +166,13 @@ def main(argv=None):
         name = os.path.splitext(os.path.basename(f))[0]
         rec = {"input": os.path.basename(f), "loss_kind": args.loss, "steps": args.steps,
                "initial_loss": float(res.initial_loss[i]), "final_loss": float(res.loss[i]),
-               "skipped": int(res.skipped[i]), "params": params_record(res.params01[i])}
+               "skipped": int(res.skipped[i]), "init": args.init, "params": params_record(res.params01[i])}
+        if res.start is not None:
+            rec["start"] = int(res.start[i])
+        if bank_idx is not None:
+            s = int(res.start[i]) if res.start is not None else 0
+            rec["bank_index"] = int(bank_idx[i, s])
+            rec["bank_distance"] = float(bank_dist[i, s])
         with open(os.path.join(args.out, name + ".params.json"), "w") as fh:
             json.dump(rec, fh, indent=1)
         write_wav(os.path.join(args.out, name + ".match.wav"), audio[i], rate)

@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""Times the spectral bank (inverse-audio-synthesis_amd/retrieval.py: SpectralBank) on one GPU and prints one JSON line.
+
+    python scripts/bench_bank.py [--reps 20] [--quality]
+
+* ias_l1_cdist at (N, M, K) = (128, 4096, 44160) and (4, 4096, 44160) (K = 345 frames x 128 mels: a mel bank of 32 x 128
+  voices of 4 s @ 44.1 kHz), against its compute floor (2 VALU instructions per (pair, k) on 256 CUs x 4 SIMD x 32 lanes
+  at 2.4 GHz) and its memory floor (the bank read once at 8 TB/s), and torch.cdist(p=1) on the same operands;
+* building that bank (32 renders and mel passes at B = 128, 4 s @ 44.1 kHz).
+``--quality``: also fit 16 targets rendered from a batch outside the bank, 200 steps of mel-L1 from the centre and from
+the 4 nearest bank voices, and report the final losses.  Kernel-level figures: run it under
+``rocprofv3 --kernel-trace --stats``."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+VALU_PER_S = 256 * 4 * 32 * 2.4e9
+
+
+def _events_ms(fn, reps):
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20, help="launches per timing")
+    ap.add_argument("--batches", type=int, default=32, help="voice batches of 128 in the bank")
+    ap.add_argument("--quality", action="store_true", help="also compare centre and bank starts over 16 targets")
+    args = ap.parse_args()
+
+    import torch
+    from inverse_audio_synthesis_amd import _lib
+    from inverse_audio_synthesis_amd.match import SoundMatcher
+    from inverse_audio_synthesis_amd.retrieval import SpectralBank
+    from inverse_audio_synthesis_amd.voice import SynthConfig, Voice
+    dev = torch.device("cuda:0")
+    lib = _lib.load()
+    B = 128
+    voice = Voice(SynthConfig(batch_size=B, sample_rate=44100, buffer_size_seconds=4.0, reproducible=False)).to(dev)
+    matcher = SoundMatcher(voice, loss="mel_l1", mel_kwargs=dict(n_fft=1024, hop_length=512, n_mels=128, power=2.0))
+    idx = range(args.batches)
+
+    SpectralBank(voice, matcher.loss, [0])                     # first use: tables, allocations
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    bank = SpectralBank(voice, matcher.loss, idx)
+    torch.cuda.synchronize()
+    build_ms = (time.perf_counter() - t0) * 1e3
+    M, K = bank.values.shape[0], bank.values[0].numel()
+    flat = bank.values.reshape(M, K)
+    out = {"bench": "spectral_bank", "M": M, "K": K, "bank_bytes": M * K * 4, "build_ms": round(build_ms, 2)}
+
+    gen = torch.Generator().manual_seed(0)
+    for N in (128, 4):
+        q = matcher.loss.target(voice.render(torch.rand((B, 78), generator=gen).to(dev)))[:N].reshape(N, K).contiguous()
+        ws = torch.empty(lib.ias_l1_cdist_workspace_bytes(N, M, K), dtype=torch.uint8, device=dev)
+        dist = torch.empty((N, M), dtype=torch.float32, device=dev)
+
+        def run():
+            lib.ias_l1_cdist(_lib.ptr(q), _lib.ptr(flat), N, M, K, _lib.ptr(ws), _lib.ptr(dist), _lib.stream())
+        ms = _events_ms(run, args.reps)
+        tc_ms = _events_ms(lambda: torch.cdist(q, flat, p=1.0), max(2, args.reps // 4))
+        ref = torch.cdist(q.double(), flat.double(), p=1.0) / K
+        out[f"cdist_{N}"] = {
+            "shape": [N, M, K], "ias_l1_cdist_us": round(ms * 1e3, 1),
+            "compute_floor_us": round(2.0 * N * M * K / VALU_PER_S * 1e6, 1),
+            "memory_floor_us": round((M + N) * K * 4 / 8e12 * 1e6, 1),
+            "torch_cdist_p1_us": round(tc_ms * 1e3, 1),
+            "max_rel_err_vs_fp64": float(((dist.double() - ref).abs() / ref.clamp_min(1e-30)).max())}
+        del ws, dist, ref
+
+    if args.quality:
+        tgt = voice.render(torch.rand((B, 78), generator=torch.Generator().manual_seed(10_000)).to(dev))[:16]
+        steps = 200
+        center = matcher.fit(tgt, steps=steps)
+        d, nb = bank.nearest(target_audio=tgt, k=4)
+        starts = bank.params01[nb.reshape(-1)].reshape(16, 4, 78)
+        fb = matcher.fit(tgt, init_params01=starts, steps=steps)
+        out["quality"] = {
+            "targets": 16, "steps": steps, "starts": 4,
+            "center_initial": [round(float(x), 4) for x in center.initial_loss],
+            "center_final": [round(float(x), 4) for x in center.loss],
+            "bank_nearest_distance": [round(float(x), 4) for x in d[:, 0]],
+            "bank_final": [round(float(x), 4) for x in fb.loss],
+            "bank_start": fb.start.tolist(),
+            "center_final_median": round(float(center.loss.median()), 4),
+            "bank_final_median": round(float(fb.loss.median()), 4),
+            "bank_better": int((fb.loss < center.loss).sum())}
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
