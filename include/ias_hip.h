@@ -380,6 +380,35 @@ long long ias_l1_cdist_workspace_bytes(int N, int M, long long K);
 int ias_l1_cdist(const float* queries, const float* bank, int N, int M, long long K, void* workspace, float* dist,
                  void* stream);
 
+/* ---- Band-limited resampling (resample.resample / resample.Resample, match_audio.py --resample): torchaudio's
+ * windowed-sinc polyphase resampler, torchaudio.functional.resample (_get_sinc_resample_kernel +
+ * _apply_sinc_resample_kernel), which the reference depends on (its requirements.txt).
+ * ias_resample_plan (HOST only, no device): plan_host[4] = {o, n, width, K} for integer rates orig -> new_:
+ *   g = gcd(orig, new_), o = orig / g, n = new_ / g, base = min(o, n) rolloff, width = ceil(lowpass_filter_width o / base),
+ *   K = 2 width + o taps per phase.  method: 0 = "sinc_interp_hann", 1 = "sinc_interp_kaiser" (beta used; torchaudio's
+ *   default 14.769656459379492).  IAS_ERR_ARG: a rate <= 0, lowpass_filter_width <= 0, rolloff outside (0, 1], another
+ *   method, |beta| > 500 or not finite with Kaiser.  IAS_ERR_UNSUPPORTED: a table of more than 16 Mi taps (n K > 2^24,
+ *   64 MB; 44100 -> 44101 would need 1.9e9).
+ * ias_resample_build_taps (HOST only): taps_host [n, K] fp32 = torchaudio's kernel computed in fp64 and rounded once:
+ *   t = clamp(((i - width) / o - j / n) base, -w, w) with w = lowpass_filter_width; window cos(t pi / w / 2)^2 (Hann) or
+ *   I0(beta sqrt(1 - (t / w)^2)) / I0(beta) (Kaiser); tap = (t == 0 ? 1 : sin(pi t) / (pi t)) (window base / o).
+ *   Same refusals as the plan.
+ * ias_resample_out_len: T_out = ceil(n T_in / o) in integer arithmetic (< 0 on bad arguments).
+ * ias_resample: y [B, T_out] (device fp32) from x [B, T_in] (device fp32, row-major, row stride T_in) and taps (device
+ *   copy of the ias_resample_build_taps table; unused and may be NULL when o == n, where y is a copy of x):
+ *   y[b, q n + j] = sum_{i < K} xpad[q o + i] taps[j][i], xpad[p] = x[b, p - width] for 0 <= p - width < T_in, else 0.
+ *   Per-row contract (as ias_l1_rows): each output is one fp32 fmaf chain over i = 0 .. K - 1 in that order, from +0; its
+ *   bits depend only on its row and the table, not on B, the row's position, the launch shape or the row's alignment.
+ *   IAS_ERR_ARG: bad pointers or sizes, K != 2 width + o.  IAS_ERR_UNSUPPORTED: B > 65535, T_out > INT_MAX, n K > 2^24,
+ *   or one output block's input window (ceil(K / o) rows of o | 1 floats) over 64 KB of LDS; nothing is launched. */
+int ias_resample_plan(int orig, int new_, int lowpass_filter_width, double rolloff, int method, double beta,
+                      int* plan_host);
+int ias_resample_build_taps(int orig, int new_, int lowpass_filter_width, double rolloff, int method, double beta,
+                            float* taps_host);
+long long ias_resample_out_len(long long T_in, int o, int n);
+int ias_resample(const float* x, const float* taps, float* y, int B, int T_in, int o, int n, int width, int K,
+                 void* stream);
+
 /* sums[3] (doubles) = column sums of partials [n][3], fixed order (deterministic); when mean_out is not
  * NULL also mean_out[0] = (float)(sums[0] * scale). */
 int ias_reduce_partials(const double* partials, long long n, double* sums, double scale, float* mean_out,

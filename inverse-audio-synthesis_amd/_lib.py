@@ -97,6 +97,10 @@ SYMBOLS = {
     "ias_mrstft_coef_rows": (_I, [_P, _P, _c.c_double, _I, _I, _P, _P]),
     "ias_l1_cdist_workspace_bytes": (_LL, [_I, _I, _LL]),
     "ias_l1_cdist": (_I, [_P, _P, _I, _I, _LL, _P, _P, _P]),
+    "ias_resample_plan": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
+    "ias_resample_build_taps": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
+    "ias_resample_out_len": (_LL, [_LL, _I, _I]),
+    "ias_resample": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ias_stft_loss_backward_mrstft_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "ias_stft_grad_frames_mrstft_rows": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "ias_stft_grad_spans_mrstft_rows": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P]),
