@@ -379,6 +379,21 @@ int ias_stft_grad_spans_mrstft_rows(const float* audio, const float* tables, int
 long long ias_l1_cdist_workspace_bytes(int N, int M, long long K);
 int ias_l1_cdist(const float* queries, const float* bank, int N, int M, long long K, void* workspace, float* dist,
                  void* stream);
+/* ias_topk_merge: the running k nearest of a streamed search (SpectralBank.search).  dist: device fp32 [N, M] with row
+ *   stride ld >= M, a block of candidate distances whose global bank indices are base + m.  best_dist [N, k] fp32 and
+ *   best_idx [N, k] int64 (device) hold the running result and are read and rewritten in place.  Per row the candidates
+ *   are the k running entries and the M new ones, ordered as retrieval.rank_distances orders them: key = the distance if
+ *   it is finite, else +inf; ascending key; equal keys by ascending global index (so non-finite distances come after
+ *   every finite one, among themselves by index).  The first k are written back in that order, each with its ORIGINAL
+ *   distance (a NaN stays a NaN) and its global index.  An empty slot is (+inf, INT64_MAX): it ranks after every real
+ *   candidate, so a fresh state is a fill and slots past the number of candidates stay empty.  The caller guarantees
+ *   that the block's indices are disjoint from the running ones.  The result is a function of the candidate set alone:
+ *   merging a bank in blocks of any sizes in any order gives the same [N, k] as one merge of everything.  One launch,
+ *   one workgroup per row.
+ *   IAS_ERR_ARG: null pointers, N < 1, M < 1, ld < M, k < 1, k > 64, base < 0 (or base + M past INT64_MAX).
+ *   IAS_ERR_UNSUPPORTED: N > 65535.  Nothing is launched on a refusal. */
+int ias_topk_merge(const float* dist, int N, int M, long long ld, long long base, int k, float* best_dist,
+                   long long* best_idx, void* stream);
 
 /* ---- Band-limited resampling (resample.resample / resample.Resample, match_audio.py --resample): torchaudio's
  * windowed-sinc polyphase resampler, torchaudio.functional.resample (_get_sinc_resample_kernel +

@@ -97,6 +97,7 @@ SYMBOLS = {
     "ias_mrstft_coef_rows": (_I, [_P, _P, _c.c_double, _I, _I, _P, _P]),
     "ias_l1_cdist_workspace_bytes": (_LL, [_I, _I, _LL]),
     "ias_l1_cdist": (_I, [_P, _P, _I, _I, _LL, _P, _P, _P]),
+    "ias_topk_merge": (_I, [_P, _I, _I, _LL, _LL, _I, _P, _P, _P]),
     "ias_resample_plan": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
     "ias_resample_build_taps": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
     "ias_resample_out_len": (_LL, [_LL, _I, _I]),

@@ -20,6 +20,15 @@
 //   v_sub_f32 and one v_add_f32 with an |.| source modifier per (pair, k).  The next slice is loaded into registers
 //   while the current one is reduced.  The chunk's fp64 sum goes to ws[chunk][n][m].
 // l1_cdist_fold_kernel: one lane per pair adds its chunk sums in chunk order.
+//
+// topk_merge_kernel (ias_topk_merge): the streamed search's running k nearest per target (SpectralBank.search).  One
+//   workgroup per row.  A candidate is (key, global index): key = rank_distances' sort key as an ordered uint32 (a
+//   non-finite distance counts as +inf, -0 as +0), the index breaks ties, so the candidates of a row are totally ordered
+//   and the k smallest do not depend on how the bank was cut into blocks.  Round r takes the workgroup-wide minimum of
+//   the candidates above round r - 1's winner: each lane scans its strided share of the block (keys staged in LDS, the
+//   part of a row past TK_CAP converted from global memory again) and, for lanes < k, its running entry held in
+//   registers since before the first barrier; a butterfly of __shfl_xor per wave, the four wave winners through LDS.
+//   The lane that owns the winner writes slot r with the original distance.  No atomics: a row belongs to one workgroup.
 #include "ias_common.h"
 #include <cstdint>
 
@@ -148,6 +157,90 @@ static void launch_chunks(const float* q, const float* b, int N, int M, long lon
                      dim3(TY * TX), 0, stream, q, b, N, M, K, ws);
 }
 
+// ------------------------------------------------------------------------------------------------ top-k merge
+#define TK_THREADS 256
+#define TK_WAVES (TK_THREADS / 64)
+#define TK_CAP 4096
+#define TK_KMAX 64
+#define TK_NONE 0xffffffffu                              // above every key (+inf maps to 0xff800000)
+
+__device__ __forceinline__ unsigned tk_key(float d) {
+  unsigned u = __float_as_uint(d);
+  if ((u & 0x7f800000u) == 0x7f800000u) u = 0x7f800000u;  // NaN, +-Inf -> +inf
+  else if (u == 0x80000000u) u = 0u;                      // -0 sorts as +0
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ bool tk_less(unsigned ka, long long ia, unsigned kb, long long ib) {
+  return ka < kb || (ka == kb && ia < ib);
+}
+
+__global__ __launch_bounds__(TK_THREADS) void topk_merge_kernel(const float* __restrict__ dist, int M, long long ld,
+                                                                long long base, int k, float* best_dist,
+                                                                long long* best_idx) {
+  __shared__ unsigned s_key[TK_CAP];
+  __shared__ unsigned s_wk[2][TK_WAVES];
+  __shared__ long long s_wi[2][TK_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* drow = dist + (size_t)blockIdx.x * ld;
+  float* bd = best_dist + (size_t)blockIdx.x * k;
+  long long* bi = best_idx + (size_t)blockIdx.x * k;
+
+  const int mc = M < TK_CAP ? M : TK_CAP;
+  for (int m = tid; m < mc; m += TK_THREADS) s_key[m] = tk_key(drow[m]);
+  // the running entry of lanes < k, read before any slot is rewritten (the barrier below); an empty slot is no candidate
+  float rd = 0.0f;
+  long long ri = INT64_MAX;
+  if (tid < k) { rd = bd[tid]; ri = bi[tid]; }
+  const unsigned rk = ri != INT64_MAX ? tk_key(rd) : TK_NONE;
+  __syncthreads();
+
+  unsigned lk = 0u;                                      // the last winner; no key is 0 and no index negative
+  long long li = -1;
+  int r = 0;
+  for (; r < k; ++r) {
+    unsigned bk = TK_NONE;
+    long long bx = INT64_MAX;
+    int bm = -1;                                         // block column of the lane's best, -1: its running entry
+    if (rk != TK_NONE && tk_less(lk, li, rk, ri)) { bk = rk; bx = ri; }
+    for (int m = tid; m < M; m += TK_THREADS) {
+      const unsigned key = m < TK_CAP ? s_key[m] : tk_key(drow[m]);
+      const long long ix = base + m;
+      if (tk_less(lk, li, key, ix) && tk_less(key, ix, bk, bx)) { bk = key; bx = ix; bm = m; }
+    }
+    unsigned wk = bk;
+    long long wi = bx;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+      const unsigned ok = __shfl_xor(wk, d, 64);
+      const long long oi = __shfl_xor(wi, d, 64);
+      if (tk_less(ok, oi, wk, wi)) { wk = ok; wi = oi; }
+    }
+    // two buffers by round parity: a wave that writes round r + 2 has passed round r + 1's barrier, which every wave
+    // reaches only after it has read round r
+    if (lane == 0) { s_wk[r & 1][wave] = wk; s_wi[r & 1][wave] = wi; }
+    __syncthreads();
+    wk = s_wk[r & 1][0];
+    wi = s_wi[r & 1][0];
+#pragma unroll
+    for (int w = 1; w < TK_WAVES; ++w) {
+      const unsigned ok = s_wk[r & 1][w];
+      const long long oi = s_wi[r & 1][w];
+      if (tk_less(ok, oi, wk, wi)) { wk = ok; wi = oi; }
+    }
+    if (wk == TK_NONE) break;                            // fewer than k candidates (the same in every lane)
+    if (bk == wk && bx == wi) {
+      bd[r] = bm >= 0 ? drow[bm] : rd;
+      bi[r] = wi;
+    }
+    lk = wk;
+    li = wi;
+  }
+  for (int j = r + tid; j < k; j += TK_THREADS) {
+    bd[j] = __uint_as_float(0x7f800000u);
+    bi[j] = INT64_MAX;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ C ABI
 static long long cdist_nchunks(long long K) { return (K + CD_CHUNK - 1) / CD_CHUNK; }
 
@@ -174,5 +267,15 @@ extern "C" int ias_l1_cdist(const float* queries, const float* bank, int N, int 
   const long long NM = (long long)N * M;
   hipLaunchKernelGGL(l1_cdist_fold_kernel, dim3((unsigned)((NM + 255) / 256)), dim3(256), 0, stream, ws, NM, nchunks,
                      (double)K, dist);
+  return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
+}
+
+extern "C" int ias_topk_merge(const float* dist, int N, int M, long long ld, long long base, int k, float* best_dist,
+                              long long* best_idx, void* stream_) {
+  if (!dist || !best_dist || !best_idx) return IAS_ERR_ARG;
+  if (N < 1 || M < 1 || ld < M || k < 1 || k > TK_KMAX || base < 0 || base > INT64_MAX - M) return IAS_ERR_ARG;
+  if (N > 65535) return IAS_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(topk_merge_kernel, dim3(N), dim3(TK_THREADS), 0, (hipStream_t)stream_, dist, M, ld, base, k,
+                     best_dist, best_idx);
   return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
 }

@@ -8,6 +8,8 @@ indices / distances of the k closest bank items.  ``torch.cdist`` is a plain lib
 ``SpectralBank`` needs no trained model: it ranks the bank voices by the sound matcher's own spectral L1 (all pairs in
 one ias_l1_cdist launch, csrc/bank_kernels.hip), the start ``match_audio.py --init bank`` uses.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -59,10 +61,11 @@ def rank_distances(dist):
     return torch.sort(key, dim=1, stable=True).indices
 
 
-def l1_cdist(queries, bank):
+def l1_cdist(queries, bank, out=None, workspace=None):
     """queries [N, K], bank [M, K] fp32 on the device (any row-major views with row stride K) -> [N, M] fp32
     sum_k |queries[n, k] - bank[m, k]| / K (ias_l1_cdist: a pair's value is the same bits whatever N, M, n, m or where the
-    rows sit in memory)."""
+    rows sit in memory).  ``out`` ([N, M] fp32, contiguous) and ``workspace`` (uint8, at least
+    ias_l1_cdist_workspace_bytes(N, M, K)) are allocated unless given (a caller in a loop reuses its own)."""
     lib = _lib.load()
     _lib.require_f32(queries, bank)
     if queries.dim() != 2 or bank.dim() != 2 or queries.shape[1] != bank.shape[1]:
@@ -71,11 +74,48 @@ def l1_cdist(queries, bank):
     M = bank.shape[0]
     nbytes = lib.ias_l1_cdist_workspace_bytes(N, M, K)
     _lib.check(min(nbytes, 0), "ias_l1_cdist_workspace_bytes")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=queries.device)
-    dist = torch.empty((N, M), dtype=torch.float32, device=queries.device)
+    if workspace is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=queries.device)
+    else:
+        ws = workspace
+        if ws.dtype != torch.uint8 or ws.numel() < nbytes:
+            raise ValueError(f"l1_cdist: workspace must be uint8 with at least {nbytes} bytes")
+    if out is None:
+        dist = torch.empty((N, M), dtype=torch.float32, device=queries.device)
+    else:
+        dist = out
+        _lib.require_f32(dist)
+        if tuple(dist.shape) != (N, M):
+            raise ValueError(f"l1_cdist: out must be [{N}, {M}], got {tuple(dist.shape)}")
     _lib.check(lib.ias_l1_cdist(_lib.ptr(queries), _lib.ptr(bank), N, M, K, _lib.ptr(ws), _lib.ptr(dist), _lib.stream()),
                "ias_l1_cdist")
     return dist
+
+
+EMPTY_INDEX = torch.iinfo(torch.int64).max              # an empty slot of a running top-k is (+inf, EMPTY_INDEX)
+
+
+def topk_merge(dist, base, best_dist, best_idx):
+    """Merge a block of candidate distances into the running k nearest per row, in place (ias_topk_merge).
+
+    dist [N, M] fp32 on the device (unit column stride, any row stride >= M): the candidates of global bank indices
+    ``base + m``, disjoint from the indices already in ``best_idx``.  best_dist [N, k] fp32, best_idx [N, k] int64
+    (contiguous, k <= 64): the running result in ``rank_distances`` order (finite distances ascending, equal ones by
+    ascending index, non-finite ones last by index), each entry with its original distance.  A fresh state is
+    ``best_dist`` filled with +inf and ``best_idx`` with ``EMPTY_INDEX``.  The result depends only on the set of
+    candidates merged so far, not on how they were cut into blocks or in which order the blocks came."""
+    lib = _lib.load()
+    _lib.require_f32(dist, best_dist)
+    if dist.dim() != 2 or best_dist.dim() != 2 or best_idx.dtype != torch.int64 or best_idx.shape != best_dist.shape \
+            or best_dist.shape[0] != dist.shape[0]:
+        raise ValueError(f"topk_merge: dist [N, M] fp32, best_dist [N, k] fp32 and best_idx [N, k] int64, got "
+                         f"{tuple(dist.shape)}, {tuple(best_dist.shape)} and {tuple(best_idx.shape)} {best_idx.dtype}")
+    N, M = dist.shape
+    if not dist.is_cuda or N < 1 or M < 1 or (M > 1 and dist.stride(1) != 1):
+        raise ValueError("topk_merge: dist must be a non-empty device tensor with unit column stride")
+    ld = dist.stride(0) if N > 1 else M
+    _lib.check(lib.ias_topk_merge(ctypes.c_void_p(dist.data_ptr()), N, M, ld, int(base), best_dist.shape[1],
+                                  _lib.ptr(best_dist), _lib.ptr(best_idx), _lib.stream()), "ias_topk_merge")
 
 
 def _bank_plan(loss):
@@ -147,3 +187,73 @@ class SpectralBank:
         k = min(int(k), d.shape[1])
         idx = rank_distances(d)[:, :k]
         return torch.gather(d, 1, idx), idx
+
+    @staticmethod
+    @torch.no_grad()
+    def search(voice, loss, batch_indices, target_audio=None, target_values=None, k=1, chunk_batches=8):
+        """``SpectralBank(voice, loss, batch_indices).nearest(...)`` without the bank in memory: the same indices and the
+        same distance bits (a pair's ias_l1_cdist value does not depend on the launch; the merge does not depend on the
+        cut), for a bank of any size -> (dist [N, k] fp32, idx [N, k] int64, params01 [N, k, 78] fp32).
+
+        The bank is rendered ``chunk_batches`` voice batches at a time into one reused [chunk_batches B, F, n_out]
+        buffer; each chunk costs one upload of its parameters from pinned memory, its renders and value passes, one
+        ias_l1_cdist and one ias_topk_merge, and the host reads nothing from the device until the loop is over.  Index
+        convention as for the resident bank: item m = j B + r is row r of ``batch_indices[j]``, rendered at row r.
+        ``params01`` is drawn again on the host for the winning batches only; ``voice.params01`` is left alone."""
+        from .voice import sample_params01
+        plan = _bank_plan(loss)
+        if (target_audio is None) == (target_values is None):
+            raise ValueError("give the target audio or its values")
+        idx = [int(i) for i in batch_indices]
+        if not idx:
+            raise ValueError("SpectralBank: no batch indices")
+        C = int(chunk_batches)
+        if C < 1:
+            raise ValueError("SpectralBank.search: chunk_batches must be >= 1")
+        C = min(C, len(idx))
+        B, T, P = voice.batch_size, voice.synthconfig.buffer_size, voice.params01.shape[1]
+        dev = voice.params01.device
+        F, n_out = plan.num_frames(T), plan.n_out
+        if target_values is None:
+            target_values = loss.target(target_audio)
+        if tuple(target_values.shape[1:]) != (F, n_out):
+            raise ValueError(f"target values must be [N, {F}, {n_out}], got {tuple(target_values.shape)}")
+        K = F * n_out
+        q = target_values.detach().to(torch.float32).contiguous().reshape(-1, K)
+        N = q.shape[0]
+        k = min(int(k), len(idx) * B)
+        if not 1 <= k <= 64:
+            raise ValueError(f"SpectralBank.search: k must be in 1..64 (ias_topk_merge), got {k}")
+
+        lib = _lib.load()
+        nbytes = lib.ias_l1_cdist_workspace_bytes(N, C * B, K)
+        _lib.check(min(nbytes, 0), "ias_l1_cdist_workspace_bytes")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        block = torch.empty(N * C * B, dtype=torch.float32, device=dev)
+        values = torch.empty((C * B, F, n_out), dtype=torch.float32, device=dev)
+        params = torch.empty((C * B, P), dtype=torch.float32, device=dev)
+        # two pinned staging buffers: the host fills one while the other's upload may still be queued behind the
+        # previous chunk's kernels; an event per buffer says when its upload has been consumed
+        staging = [torch.empty((C * B, P), dtype=torch.float32, pin_memory=True) for _ in range(2)]
+        uploaded = [torch.cuda.Event(), torch.cuda.Event()]
+        best_dist = torch.full((N, k), float("inf"), dtype=torch.float32, device=dev)
+        best_idx = torch.full((N, k), EMPTY_INDEX, dtype=torch.int64, device=dev)
+        for c, j0 in enumerate(range(0, len(idx), C)):
+            chunk = idx[j0:j0 + C]
+            n = len(chunk)
+            host = staging[c & 1]
+            if c >= 2:
+                uploaded[c & 1].synchronize()
+            for j, i in enumerate(chunk):
+                host[j * B:(j + 1) * B] = sample_params01(B, i)
+            params[:n * B].copy_(host[:n * B], non_blocking=True)
+            uploaded[c & 1].record()
+            for j in range(n):
+                values[j * B:(j + 1) * B] = loss.target(voice.render(params[j * B:(j + 1) * B], normalize=True))
+            d = l1_cdist(q, values[:n * B].reshape(n * B, K), out=block[:N * n * B].view(N, n * B), workspace=ws)
+            topk_merge(d, j0 * B, best_dist, best_idx)
+
+        win = best_idx.cpu()
+        batches, which = torch.unique(win // B, return_inverse=True)
+        draws = torch.stack([sample_params01(B, idx[j]) for j in batches.tolist()])
+        return best_dist, best_idx, draws[which, win % B].to(dev)

@@ -2,7 +2,7 @@
 """Sound matching entry point: fit the 78 Voice parameters to WAV files.
 
     python match_audio.py in1.wav in2.wav --steps 200 --out DIR [--init center|random|bank] [--starts S]
-                          [--bank-batches NB] [--loss LOSS] [key=value ...]
+                          [--bank-batches NB] [--bank-stream CHUNK] [--loss LOSS] [key=value ...]
 
 ``key=value`` are config overrides as for pretrain.py / audio_to_params.py (``torchsynth.rate``,
 ``torchsynth.buffer_size_seconds``, ``mel.*``); the matcher's own settings are flags.  Input WAVs are 16-, 24- or 32-bit
@@ -14,7 +14,9 @@ parameter in 0..1 and in its own units, the loss, its initial and final value) a
 whose 1.1 ms hop constrains the envelopes' short segments better).  ``--init``: center (every parameter 0.5), random
 (``--starts`` draws per sound) or bank: a ``retrieval.SpectralBank`` of ``--bank-batches`` x 128 random voices is rendered
 and each sound starts from its ``--starts`` nearest voices under the matcher's loss (a mel bank for
-multi_resolution_stft); the best start is kept and the JSON record names it (``bank_index``, ``bank_distance``)."""
+multi_resolution_stft); the best start is kept and the JSON record names it (``bank_index``, ``bank_distance``).  With
+``--bank-stream CHUNK`` the bank is not kept: ``SpectralBank.search`` renders it CHUNK batches at a time and keeps the
+running nearest voices, with the same result, so ``--bank-batches`` is bounded by time and not by memory."""
 import argparse
 import json
 import os
@@ -126,6 +128,8 @@ def parse_args(argv=None):
     ap.add_argument("--init", choices=INITS, default="center")
     ap.add_argument("--starts", type=int, default=1, help="starts per sound (--init random or bank; center: 1)")
     ap.add_argument("--bank-batches", type=int, default=32, help="--init bank: voice batches of 128 in the bank")
+    ap.add_argument("--bank-stream", type=int, default=None, metavar="CHUNK",
+                    help="--init bank: search the bank CHUNK batches at a time instead of keeping it in memory")
     ap.add_argument("--loss", choices=("mel_l1", "stft_l1", "multi_resolution_stft"), default="mel_l1")
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--beta1", type=float, default=0.9)
@@ -147,6 +151,13 @@ def parse_args(argv=None):
         ap.error("--init center has one start per sound: --starts must be 1")
     if args.bank_batches < 1:
         ap.error("--bank-batches must be >= 1")
+    if args.bank_stream is not None:
+        if args.init != "bank":
+            ap.error("--bank-stream needs --init bank")
+        if args.bank_stream < 1:
+            ap.error("--bank-stream must be >= 1")
+        if args.starts > 64:
+            ap.error("--bank-stream keeps at most 64 starts per sound")
     return args, files, overrides
 
 
@@ -190,14 +201,23 @@ def main(argv=None):
             bank_loss = MelSpectrogramL1(**kw).to(dev)
         else:
             bank_loss = matcher.loss
-        nbytes = SpectralBank.nbytes(bank_voice, bank_loss, args.bank_batches)
-        print(f"match_audio.py: building a spectral bank of {args.bank_batches * BANK_BATCH} voices "
-              f"({nbytes} bytes)", flush=True)
-        bank = SpectralBank(bank_voice, bank_loss, range(args.bank_batches))
-        bank_dist, bank_idx = bank.nearest(target_audio=target, k=nS)
-        nS = bank_idx.shape[1]
-        init = bank.params01[bank_idx.reshape(-1)].reshape(N, nS, 78)
-        del bank
+        if args.bank_stream is not None:
+            chunk = min(args.bank_stream, args.bank_batches)
+            nbytes = SpectralBank.nbytes(bank_voice, bank_loss, chunk)
+            print(f"match_audio.py: searching a spectral bank of {args.bank_batches * BANK_BATCH} voices in chunks of "
+                  f"{chunk * BANK_BATCH} ({nbytes} bytes)", flush=True)
+            bank_dist, bank_idx, init = SpectralBank.search(bank_voice, bank_loss, range(args.bank_batches),
+                                                            target_audio=target, k=nS, chunk_batches=chunk)
+            nS = bank_idx.shape[1]
+        else:
+            nbytes = SpectralBank.nbytes(bank_voice, bank_loss, args.bank_batches)
+            print(f"match_audio.py: building a spectral bank of {args.bank_batches * BANK_BATCH} voices "
+                  f"({nbytes} bytes)", flush=True)
+            bank = SpectralBank(bank_voice, bank_loss, range(args.bank_batches))
+            bank_dist, bank_idx = bank.nearest(target_audio=target, k=nS)
+            nS = bank_idx.shape[1]
+            init = bank.params01[bank_idx.reshape(-1)].reshape(N, nS, 78)
+            del bank
     else:
         init = None
     res = matcher.fit(target, init_params01=init, steps=args.steps, return_audio=True)
