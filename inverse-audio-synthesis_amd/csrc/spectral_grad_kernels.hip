@@ -234,9 +234,40 @@ __global__ __launch_bounds__(SG_THREADS) void stft_grad_frames_kernel(SgArgs g) 
   }   // frame pairs
 }
 
+// The padded positions that read sample j of a row of T samples, reflect-padded by `pad` on both sides: itself and its
+// (at most two) reflections -> qs; returns how many.
+__device__ __forceinline__ int sg_reflect_reads(int j, int T, int pad, int (&qs)[3]) {
+  int nq = 0;
+  qs[nq++] = j + pad;
+  if (j >= 1 && j <= pad) qs[nq++] = pad - j;
+  if (j <= T - 2 && j >= T - 1 - pad) qs[nq++] = pad + 2 * (T - 1) - j;
+  return nq;
+}
+
+// Padded position q of a row from its chunk spans sp (ias_stft_grad_spans): span c covers [c G hop, c G hop + L) with the
+// sum over ITS frames; c = min(q / (G hop), chunks - 1), so q lies in span c and possibly in span c - 1 (G hop >= N - hop),
+// added lower chunk first.
+__device__ __forceinline__ float sg_span_value(const float* __restrict__ sp, int q, int c, int N, int hop, int G, int L, int F) {
+  const int gh = G * hop;
+  float v = 0.0f;
+  if (c >= 1 && q - (c - 1) * gh < L) v = sp[(size_t)(c - 1) * L + (q - (c - 1) * gh)];
+  const int nf = min(F, (c + 1) * G) - c * G;             // frames of chunk c (the last one may be short)
+  if (q - c * gh < (nf - 1) * hop + N) v += sp[(size_t)c * L + (q - c * gh)];
+  return v;
+}
+
+// acc times the cotangent: the device scalar g_loss[0] (NULL = 1) or, ROWS, the row's g_loss[b], exactly 0 where that is 0.
+template <bool ROWS>
+__device__ __forceinline__ float sg_scaled(float acc, const float* __restrict__ g_loss, int b) {
+  if constexpr (ROWS) {
+    const float g = g_loss[b];
+    return g == 0.0f ? 0.0f : acc * g;
+  }
+  return g_loss ? acc * g_loss[0] : acc;
+}
+
 // g_audio[b,j] = g_loss * sum over the padded positions q that read audio[j] (itself and its reflections) of the
-// frames covering q.  ROWS: the cotangent is the device vector g_loss[B] (the per-sound losses, ias_stft_loss_backward_rows),
-// and a row whose g_loss[b] is 0 gets exactly 0.
+// frames covering q.  ROWS: the cotangent is the device vector g_loss[B] (the per-sound losses, ias_stft_loss_backward_rows).
 template <bool ROWS>
 __global__ __launch_bounds__(SG_THREADS) void stft_grad_ola_kernel(const float* __restrict__ frame_grad,
                                                                    const float* __restrict__ g_loss,
@@ -247,29 +278,18 @@ __global__ __launch_bounds__(SG_THREADS) void stft_grad_ola_kernel(const float* 
   const int pad = N / 2;
   const float* fg = frame_grad + (size_t)b * F * N;
   int qs[3];
-  int nq = 0;
-  qs[nq++] = j + pad;
-  if (j >= 1 && j <= pad) qs[nq++] = pad - j;
-  if (j <= T - 2 && j >= T - 1 - pad) qs[nq++] = pad + 2 * (T - 1) - j;
   float acc = 0.0f;
-  for (int i = 0; i < nq; ++i) {
+  for (int i = 0, nq = sg_reflect_reads(j, T, pad, qs); i < nq; ++i) {
     const int q = qs[i];
     int f_hi = q / hop;
     if (f_hi > F - 1) f_hi = F - 1;
     int f_lo = q - N + 1 <= 0 ? 0 : (q - N + 1 + hop - 1) / hop;
     for (int f = f_lo; f <= f_hi; ++f) acc += fg[(size_t)f * N + (q - f * hop)];
   }
-  if constexpr (ROWS) {
-    const float g = g_loss[b];
-    g_audio[(size_t)b * T + j] = g == 0.0f ? 0.0f : acc * g;
-  } else {
-    g_audio[(size_t)b * T + j] = g_loss ? acc * g_loss[0] : acc;
-  }
+  g_audio[(size_t)b * T + j] = sg_scaled<ROWS>(acc, g_loss, b);
 }
 
-// The same from chunk spans (ias_stft_grad_spans): span c of row b covers the padded samples [c G hop, c G hop + L) with
-// the sum over ITS frames; a sample lies in at most two spans (G hop >= N - hop), added lower chunk first.  ROWS: as in
-// stft_grad_ola_kernel.
+// The same from the chunk spans of ias_stft_grad_spans (sg_span_value).
 template <bool ROWS>
 __global__ __launch_bounds__(SG_THREADS) void stft_grad_combine_kernel(const float* __restrict__ spans,
                                                                        const float* __restrict__ g_loss,
@@ -280,27 +300,14 @@ __global__ __launch_bounds__(SG_THREADS) void stft_grad_combine_kernel(const flo
   const int pad = N / 2, gh = G * hop;
   const float* sp = spans + (size_t)b * cper * L;
   int qs[3];
-  int nq = 0;
-  qs[nq++] = j + pad;
-  if (j >= 1 && j <= pad) qs[nq++] = pad - j;
-  if (j <= T - 2 && j >= T - 1 - pad) qs[nq++] = pad + 2 * (T - 1) - j;
   float acc = 0.0f;
-  for (int i = 0; i < nq; ++i) {
+  for (int i = 0, nq = sg_reflect_reads(j, T, pad, qs); i < nq; ++i) {
     const int q = qs[i];
     int c = q / gh;
     if (c > cper - 1) c = cper - 1;
-    float v = 0.0f;
-    if (c >= 1 && q - (c - 1) * gh < L) v = sp[(size_t)(c - 1) * L + (q - (c - 1) * gh)];
-    const int nf = min(F, (c + 1) * G) - c * G;             // frames of chunk c (the last one may be short)
-    if (q - c * gh < (nf - 1) * hop + N) v += sp[(size_t)c * L + (q - c * gh)];
-    acc += v;
+    acc += sg_span_value(sp, q, c, N, hop, G, L, F);
   }
-  if constexpr (ROWS) {
-    const float g = g_loss[b];
-    g_audio[(size_t)b * T + j] = g == 0.0f ? 0.0f : acc * g;
-  } else {
-    g_audio[(size_t)b * T + j] = g_loss ? acc * g_loss[0] : acc;
-  }
+  g_audio[(size_t)b * T + j] = sg_scaled<ROWS>(acc, g_loss, b);
 }
 
 // Several resolutions at once (MR-STFT): g_audio = g_loss * sum over the resolutions, in their order, of the above --
@@ -317,21 +324,13 @@ __device__ __forceinline__ float combine_one(const CombineArgs& a, int r, const 
   const int N = a.N[r], hop = a.hop[r], G = a.G[r], cper = a.cper[r], L = a.L[r], F = a.F[r];
   const int pad = N / 2, gh = G * hop;
   int qs[3];
-  int nq = 0;
-  qs[nq++] = j + pad;
-  if (j >= 1 && j <= pad) qs[nq++] = pad - j;
-  if (j <= T - 2 && j >= T - 1 - pad) qs[nq++] = pad + 2 * (T - 1) - j;
   float acc = 0.0f;
-  for (int i = 0; i < nq; ++i) {
+  for (int i = 0, nq = sg_reflect_reads(j, T, pad, qs); i < nq; ++i) {
     const int q = qs[i];
     int c = (int)__umulhi((unsigned)q, a.magic[r]);         // floor(q / gh) or one less
     if (q - c * gh >= gh) ++c;
     if (c > cper - 1) c = cper - 1;
-    float v = 0.0f;
-    if (c >= 1 && q - (c - 1) * gh < L) v = sp[(size_t)(c - 1) * L + (q - (c - 1) * gh)];
-    const int nf = min(F, (c + 1) * G) - c * G;
-    if (q - c * gh < (nf - 1) * hop + N) v += sp[(size_t)c * L + (q - c * gh)];
-    acc += v;
+    acc += sg_span_value(sp, q, c, N, hop, G, L, F);
   }
   return acc;
 }
@@ -357,7 +356,7 @@ __global__ __launch_bounds__(SG_THREADS) void stft_grad_combine_multi_kernel(con
       int c = (int)__umulhi((unsigned)q, a.magic[r]);
       if (q - c * gh >= gh) ++c;
       if (c > cper - 1) c = cper - 1;
-      const int off = q - c * gh;
+      const int off = q - c * gh;                           // sg_span_value for q and q + 1 at once
       float2 lo = make_float2(0.0f, 0.0f), hi = make_float2(0.0f, 0.0f);
       if (c >= 1 && off + gh < L) lo = *reinterpret_cast<const float2*>(sp + (size_t)(c - 1) * L + off + gh);
       const int nf = min(F, (c + 1) * G) - c * G;
@@ -535,7 +534,7 @@ extern "C" int ias_stft_loss_backward_mrstft_rows(const float* audio, const floa
 // The few scalar operations between the fused reductions and the backward kernels, as one launch each instead of a
 // dozen at::native elementwise launches per resolution (profiles/r03b_kstats_gradstep.csv: 6 % of the gradient step's
 // kernel time and most of its launch count).  fp64, the same operations in the same order as the torch expressions
-// they replace (spectral.py: MultiResolutionSTFTLoss._forward, _mrstft_plan_backward).
+// they replace (spectral.py: MultiResolutionSTFTLoss._forward, _MRSTFTFn.backward).
 #define IAS_MR_MAX_RES 8
 struct MrTotalArgs { const double* sums[IAS_MR_MAX_RES]; double count[IAS_MR_MAX_RES]; int nres; };
 

@@ -8,9 +8,10 @@ Per chunk of ``voice.batch_size`` targets, every iteration is
 
     audio = voice.render(p)                      HIP render with its adjoint (voice_grad.py), normalize=True
     L     = loss.per_item(audio, target)         [B] per-sound spectral L1 or MR-STFT (spectral.py, csrc/match_kernels.hip)
-    L.backward(active)                           per-row cotangent (ias_stft_loss_backward_rows, ias_mrstft_coef_rows +
-                                                 the *_mrstft_rows span / frame kernels): a sound's gradient
-                                                 does not depend on the batch, padded rows get exactly 0
+    L.backward(active)                           per-row cotangent (the ``rows`` form of spectral._L1Fn / _MRSTFTFn:
+                                                 ias_stft_loss_backward_rows, ias_mrstft_coef_rows + the *_mrstft_rows
+                                                 span / frame kernels): a sound's gradient does not depend on the
+                                                 batch, padded rows get exactly 0
     ias_match_adam_step                          best-so-far, non-finite skip, Adam per row, clamp to [0, 1]
 
 with all state on the device and no host read inside the loop.

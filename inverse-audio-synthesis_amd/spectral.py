@@ -132,14 +132,18 @@ class STFTPlan(nn.Module):
         _lib.check(min(F, 0), "ias_stft_num_frames (need T > n_fft/2 for reflect padding)")
         return F
 
+    def _mel_args(self):
+        """(mel_start, mel_count, mel_woff, mel_w, nnz): the CSR filterbank as the C entries take it (linear bins: NULLs, 0)."""
+        if self.n_mels is None:
+            return None, None, None, None, 0
+        return (_lib.ptr(self.mel_start), _lib.ptr(self.mel_count), _lib.ptr(self.mel_woff), _lib.ptr(self.mel_w),
+                int(self.mel_w.numel()))
+
     def _call(self, audio, out, target, partials, value_mode, loss_mode, eps, rowpeak=None):
         lib = _lib.load()
         B, T = audio.shape
-        mel = self.n_mels is not None
         st = lib.ias_stft(_lib.ptr(audio), _lib.ptr(self.tables), _lib.ptr(self.mtables), _lib.ptr(self.segtab),
-                          _lib.ptr(self.mel_start) if mel else None, _lib.ptr(self.mel_count) if mel else None,
-                          _lib.ptr(self.mel_woff) if mel else None, _lib.ptr(self.mel_w) if mel else None,
-                          int(self.mel_w.numel()) if mel else 0, _lib.ptr(out), _lib.ptr(target), _lib.ptr(partials),
+                          *self._mel_args(), _lib.ptr(out), _lib.ptr(target), _lib.ptr(partials),
                           _lib.ptr(rowpeak), _lib.ptr(self._ticket(audio.device)), B, T, self.n_fft, self.hop_length,
                           self.n_out, value_mode, loss_mode, float(eps), _lib.stream())
         _lib.check(st, "ias_stft")
@@ -196,118 +200,83 @@ class STFTPlan(nn.Module):
         return sums if mean is None else mean
 
 
-    def l1_rows(self, values, target_values):
-        """Per-row mean |values - target| of two [B, frames, n_out] tensors -> [B] fp32 (ias_l1_rows: fixed order, a row's
-        result the same bits wherever it sits in the batch)."""
+    def _rows_reduce(self, entry, values, target_values, width, dtype):
+        """``entry`` (ias_l1_rows / ias_mrstft_rows) over the rows of two [B, frames, n_out] tensors: per-chunk fp64 partials
+        [B, chunks, *width], folded in fixed order -> [B, *width] of ``dtype``."""
         lib = _lib.load()
         assert values.shape == target_values.shape and values.is_contiguous() and target_values.is_contiguous()
         _lib.require_f32(values, target_values)
         B = values.shape[0]
         n = values[0].numel()
-        nch = lib.ias_l1_rows_partials_count(n)
-        _lib.check(min(nch, 0), "ias_l1_rows_partials_count")
-        partials = torch.empty((B, nch), dtype=torch.float64, device=values.device)
-        out = torch.empty(B, dtype=torch.float32, device=values.device)
-        _lib.check(lib.ias_l1_rows(_lib.ptr(values), _lib.ptr(target_values), B, n, _lib.ptr(partials), _lib.ptr(out),
-                                   _lib.stream()), "ias_l1_rows")
+        nch = getattr(lib, entry + "_partials_count")(n)
+        _lib.check(min(nch, 0), entry + "_partials_count")
+        partials = torch.empty((B, nch) + width, dtype=torch.float64, device=values.device)
+        out = torch.empty((B,) + width, dtype=dtype, device=values.device)
+        _lib.check(getattr(lib, entry)(_lib.ptr(values), _lib.ptr(target_values), B, n, _lib.ptr(partials), _lib.ptr(out),
+                                       _lib.stream()), entry)
         return out
+
+    def l1_rows(self, values, target_values):
+        """Per-row mean |values - target| of two [B, frames, n_out] tensors -> [B] fp32 (ias_l1_rows: fixed order, a row's
+        result the same bits wherever it sits in the batch)."""
+        return self._rows_reduce("ias_l1_rows", values, target_values, (), torch.float32)
 
     def mrstft_rows(self, values, target_values):
         """Per-row MR-STFT sums of one resolution: two [B, frames, n_out] tensors of clamped magnitudes -> [B, 3] fp64
         {sum (T - V)^2, sum T^2, sum |ln V - ln T|} (ias_mrstft_rows: fixed order, a row's sums the same bits wherever it
         sits in the batch)."""
-        lib = _lib.load()
-        assert values.shape == target_values.shape and values.is_contiguous() and target_values.is_contiguous()
-        _lib.require_f32(values, target_values)
-        B = values.shape[0]
-        n = values[0].numel()
-        nch = lib.ias_mrstft_rows_partials_count(n)
-        _lib.check(min(nch, 0), "ias_mrstft_rows_partials_count")
-        partials = torch.empty((B, nch, 3), dtype=torch.float64, device=values.device)
-        sums = torch.empty((B, 3), dtype=torch.float64, device=values.device)
-        _lib.check(lib.ias_mrstft_rows(_lib.ptr(values), _lib.ptr(target_values), B, n, _lib.ptr(partials), _lib.ptr(sums),
-                                       _lib.stream()), "ias_mrstft_rows")
-        return sums
+        return self._rows_reduce("ias_mrstft_rows", values, target_values, (3,), torch.float64)
 
 
-class _L1LossFn(torch.autograd.Function):
-    """mean |V(audio) - target| with the fused HIP forward and the HIP adjoint w.r.t. the audio."""
+class _L1Fn(torch.autograd.Function):
+    """mean |V(audio) - target| with the HIP adjoint w.r.t. the audio: the scalar over the batch (the fused forward, a
+    cotangent [1]: ias_stft_loss_backward) or, ``rows``, the [B] per-sound means (the values pass, then ias_l1_rows; a
+    cotangent per row: ias_stft_loss_backward_rows)."""
 
     @staticmethod
-    def forward(ctx, audio, plan, target_values, value_mode):
+    def forward(ctx, audio, plan, target_values, value_mode, rows):
         a = plan._audio2d(audio)
-        ctx.plan, ctx.value_mode, ctx.shape = plan, value_mode, audio.shape
+        ctx.plan, ctx.value_mode, ctx.rows, ctx.shape = plan, value_mode, rows, audio.shape
         ctx.save_for_backward(a, target_values)
+        if rows:
+            assert target_values.shape == (a.shape[0], plan.num_frames(a.shape[1]), plan.n_out)
+            return plan.l1_rows(plan.values(a, value_mode), target_values)
         return plan.loss_sums(a, target_values, value_mode, LOSS_L1, mean_scale=1.0 / target_values.numel())
 
     @staticmethod
-    def backward(ctx, g_loss):
+    def backward(ctx, g):
         a, target = ctx.saved_tensors
         plan = ctx.plan
         lib = _lib.load()
         B, T = a.shape
         F = plan.num_frames(T)
-        mel = plan.n_mels is not None
         frame_grad = torch.empty((B, F, plan.n_fft), dtype=torch.float32, device=a.device)
         g_audio = torch.empty_like(a)
-        gl = g_loss.to(torch.float32).reshape(1).contiguous()
-        st = lib.ias_stft_loss_backward(
-            _lib.ptr(a), _lib.ptr(plan.window), _lib.ptr(plan.tables), _lib.ptr(plan.mel_start) if mel else None,
-            _lib.ptr(plan.mel_count) if mel else None, _lib.ptr(plan.mel_woff) if mel else None,
-            _lib.ptr(plan.mel_w) if mel else None, int(plan.mel_w.numel()) if mel else 0, _lib.ptr(target), _lib.ptr(gl),
-            None, _lib.ptr(frame_grad),
-            _lib.ptr(g_audio), B, T, plan.n_fft, plan.hop_length, plan.n_out,
-            2 if ctx.value_mode == VALUE_POWER else 1, LOSS_L1, 1.0 / target.numel(), 0.0, _lib.stream())
-        _lib.check(st, "ias_stft_loss_backward")
-        return g_audio.reshape(ctx.shape), None, None, None
+        g32 = g.to(torch.float32).reshape(B if ctx.rows else 1).contiguous()
+        head = (_lib.ptr(a), _lib.ptr(plan.window), _lib.ptr(plan.tables), *plan._mel_args(), _lib.ptr(target), _lib.ptr(g32))
+        tail = (_lib.ptr(frame_grad), _lib.ptr(g_audio), B, T, plan.n_fft, plan.hop_length, plan.n_out,
+                2 if ctx.value_mode == VALUE_POWER else 1)
+        if ctx.rows:
+            st = lib.ias_stft_loss_backward_rows(*head, *tail, 1.0 / (F * plan.n_out), _lib.stream())
+        else:
+            st = lib.ias_stft_loss_backward(*head, None, *tail, LOSS_L1, 1.0 / target.numel(), 0.0, _lib.stream())
+        _lib.check(st, "ias_stft_loss_backward_rows" if ctx.rows else "ias_stft_loss_backward")
+        return g_audio.reshape(ctx.shape), None, None, None, None
 
 
 def _l1_loss(plan, audio, target_values, value_mode, rowpeak=None, reduce_stream=None):
     if torch.is_grad_enabled() and audio.requires_grad:
         assert value_mode in (VALUE_POWER, VALUE_MAG)
         assert rowpeak is None, "the folded normalisation is a forward-only path"
-        return _L1LossFn.apply(audio, plan, target_values, value_mode)
+        return _L1Fn.apply(audio, plan, target_values, value_mode, False)
     return plan.loss_sums(audio, target_values, value_mode, LOSS_L1, mean_scale=1.0 / target_values.numel(),
                           rowpeak=rowpeak, reduce_stream=reduce_stream)
-
-
-class _L1RowsFn(torch.autograd.Function):
-    """[B] per-sound mean |V(audio) - target| (the values pass, then ias_l1_rows) with the HIP adjoint w.r.t. the audio for
-    a cotangent per row (ias_stft_loss_backward_rows)."""
-
-    @staticmethod
-    def forward(ctx, audio, plan, target_values, value_mode):
-        a = plan._audio2d(audio)
-        assert target_values.shape == (a.shape[0], plan.num_frames(a.shape[1]), plan.n_out)
-        ctx.plan, ctx.value_mode, ctx.shape = plan, value_mode, audio.shape
-        ctx.save_for_backward(a, target_values)
-        return plan.l1_rows(plan.values(a, value_mode), target_values)
-
-    @staticmethod
-    def backward(ctx, g_rows):
-        a, target = ctx.saved_tensors
-        plan = ctx.plan
-        lib = _lib.load()
-        B, T = a.shape
-        F = plan.num_frames(T)
-        mel = plan.n_mels is not None
-        frame_grad = torch.empty((B, F, plan.n_fft), dtype=torch.float32, device=a.device)
-        g_audio = torch.empty_like(a)
-        g = g_rows.to(torch.float32).reshape(B).contiguous()
-        st = lib.ias_stft_loss_backward_rows(
-            _lib.ptr(a), _lib.ptr(plan.window), _lib.ptr(plan.tables), _lib.ptr(plan.mel_start) if mel else None,
-            _lib.ptr(plan.mel_count) if mel else None, _lib.ptr(plan.mel_woff) if mel else None,
-            _lib.ptr(plan.mel_w) if mel else None, int(plan.mel_w.numel()) if mel else 0, _lib.ptr(target), _lib.ptr(g),
-            _lib.ptr(frame_grad), _lib.ptr(g_audio), B, T, plan.n_fft, plan.hop_length, plan.n_out,
-            2 if ctx.value_mode == VALUE_POWER else 1, 1.0 / (F * plan.n_out), _lib.stream())
-        _lib.check(st, "ias_stft_loss_backward_rows")
-        return g_audio.reshape(ctx.shape), None, None, None
 
 
 def _l1_rows(plan, audio, target_values, value_mode):
     assert value_mode in (VALUE_POWER, VALUE_MAG)
     if torch.is_grad_enabled() and audio.requires_grad:
-        return _L1RowsFn.apply(audio, plan, target_values, value_mode)
+        return _L1Fn.apply(audio, plan, target_values, value_mode, True)
     a = plan._audio2d(audio)
     return plan.l1_rows(plan.values(a, value_mode), target_values)
 
@@ -411,8 +380,8 @@ class MultiResolutionSTFTLoss(nn.Module):
         if targets is None:
             targets = self.target(y)
         if torch.is_grad_enabled() and x.requires_grad:
-            return _MRSTFTFn.apply(x, self, *targets)
-        return self._forward(x, targets)[0]
+            return _MRSTFTFn.apply(x, self, False, *targets)
+        return self._forward(STFTPlan._audio2d(x), targets, False)[0]
 
     def per_item(self, x, y=None, targets=None):
         """[B] fp32: the loss of each sound on its own (``forward`` applied to row b alone; at B = 1 the same value up to
@@ -423,8 +392,8 @@ class MultiResolutionSTFTLoss(nn.Module):
             targets = self.target(y)
         targets = [t.detach().contiguous() for t in targets]
         if torch.is_grad_enabled() and x.requires_grad:
-            return _MRSTFTRowsFn.apply(x, self, *targets)
-        return self._forward_rows(STFTPlan._audio2d(x), targets)[0]
+            return _MRSTFTFn.apply(x, self, True, *targets)
+        return self._forward(STFTPlan._audio2d(x), targets, True)[0]
 
     def _streams(self, device):
         """One side stream per resolution (created once per device).  The kernels of the three resolutions are latency
@@ -435,242 +404,141 @@ class MultiResolutionSTFTLoss(nn.Module):
             pool[device] = [torch.cuda.Stream(device) for _ in self.plans]
         return pool[device]
 
-    def _forward(self, x, targets):
-        cur = torch.cuda.current_stream(x.device) if x.is_cuda else None
-        streams = self._streams(x.device) if (x.is_cuda and self.parallel) else None
-        sums = []
-        for k, (plan, tgt) in enumerate(zip(self.plans, targets)):
-            if streams is None:
-                sums.append(plan.loss_sums(x, tgt, VALUE_MAG_CLAMPED, LOSS_MRSTFT, self.eps))
-            else:
-                streams[k].wait_stream(cur)
-                with torch.cuda.stream(streams[k]):
-                    s = plan.loss_sums(x, tgt, VALUE_MAG_CLAMPED, LOSS_MRSTFT, self.eps)
-                    s.record_stream(cur)
-                    sums.append(s)
-        saved = []
-        for k, (tgt, s) in enumerate(zip(targets, sums)):
-            if streams is not None:
-                cur.wait_stream(streams[k])
-            saved.append((tgt, s))
-        # (sum_k sqrt(s_k[0]) / sqrt(s_k[1]) + s_k[2] / count_k) / nres in fp64 -> fp32, one launch
-        n = len(sums)
-        loss = torch.empty((), dtype=torch.float32, device=x.device)
-        ptrs = (ctypes.c_void_p * n)(*[s.data_ptr() for s in sums])
-        counts = (ctypes.c_double * n)(*[float(t.numel()) for t in targets])
-        _lib.check(_lib.load().ias_mrstft_total(ptrs, counts, n, _lib.ptr(loss), _lib.stream()), "ias_mrstft_total")
-        return loss, saved
+    def _each_resolution(self, device, fn):
+        """[fn(k, plan) for every resolution]: a tensor each.  ``parallel``: resolution k on side stream k, forked from the
+        caller's stream just before its body; every result is handed to the caller's stream, which then waits for the side
+        streams in resolution order.  Otherwise one after the other on the caller's stream."""
+        if not (self.parallel and device.type == "cuda"):      # (a host tensor is refused by the first kernel call)
+            return [fn(k, plan) for k, plan in enumerate(self.plans)]
+        cur = torch.cuda.current_stream(device)
+        streams = self._streams(device)
+        outs = []
+        for k, plan in enumerate(self.plans):
+            streams[k].wait_stream(cur)
+            with torch.cuda.stream(streams[k]):
+                out = fn(k, plan)
+                out.record_stream(cur)
+                outs.append(out)
+        for st in streams[:len(outs)]:
+            cur.wait_stream(st)
+        return outs
 
-    def _forward_rows(self, a, targets):
-        """Per resolution the values pass and ias_mrstft_rows (on the side streams when ``parallel``), then one
-        ias_mrstft_rows_total on the caller's stream -> ([B] fp32, [B, 3] fp64 sums per resolution)."""
+    def _forward(self, a, targets, rows):
+        """Per resolution the three sums of the batch (the fused ``loss_sums``) or, ``rows``, of every row (the values pass
+        and ias_mrstft_rows), then one launch on the caller's stream for
+        (sum_k sqrt(s_k[0]) / sqrt(s_k[1]) + s_k[2] / count_k) / nres in fp64 -> fp32
+        -> (the scalar or [B] fp32, the sums per resolution: [3] or [B, 3] fp64)."""
         B = a.shape[0]
-        cur = torch.cuda.current_stream(a.device)
-        streams = self._streams(a.device) if self.parallel else None
-        sums = []
-        for k, (plan, tgt) in enumerate(zip(self.plans, targets)):
-            assert tgt.shape == (B, plan.num_frames(a.shape[1]), plan.n_out)
-            if streams is None:
-                sums.append(plan.mrstft_rows(plan.values(a, VALUE_MAG_CLAMPED, self.eps), tgt))
-            else:
-                streams[k].wait_stream(cur)
-                with torch.cuda.stream(streams[k]):
-                    s = plan.mrstft_rows(plan.values(a, VALUE_MAG_CLAMPED, self.eps), tgt)
-                    s.record_stream(cur)
-                    sums.append(s)
-        if streams is not None:
-            for st in streams[:len(sums)]:
-                cur.wait_stream(st)
+
+        def sums_of(k, plan):
+            if not rows:
+                return plan.loss_sums(a, targets[k], VALUE_MAG_CLAMPED, LOSS_MRSTFT, self.eps)
+            assert targets[k].shape == (B, plan.num_frames(a.shape[1]), plan.n_out)
+            return plan.mrstft_rows(plan.values(a, VALUE_MAG_CLAMPED, self.eps), targets[k])
+
+        sums = self._each_resolution(a.device, sums_of)
         n = len(sums)
-        out = torch.empty(B, dtype=torch.float32, device=a.device)
+        out = torch.empty(B if rows else (), dtype=torch.float32, device=a.device)
         ptrs = (ctypes.c_void_p * n)(*[s.data_ptr() for s in sums])
-        counts = (ctypes.c_double * n)(*[float(t[0].numel()) for t in targets])
-        _lib.check(_lib.load().ias_mrstft_rows_total(ptrs, counts, n, B, _lib.ptr(out), _lib.stream()),
-                   "ias_mrstft_rows_total")
+        counts = (ctypes.c_double * n)(*[float((t[0] if rows else t).numel()) for t in targets])
+        lib = _lib.load()
+        if rows:
+            _lib.check(lib.ias_mrstft_rows_total(ptrs, counts, n, B, _lib.ptr(out), _lib.stream()), "ias_mrstft_rows_total")
+        else:
+            _lib.check(lib.ias_mrstft_total(ptrs, counts, n, _lib.ptr(out), _lib.stream()), "ias_mrstft_total")
         return out, sums
 
 
 class _MRSTFTFn(torch.autograd.Function):
-    """MultiResolutionSTFTLoss with the HIP adjoint w.r.t. the prediction (the target gets no gradient)."""
+    """MultiResolutionSTFTLoss with the HIP adjoint w.r.t. the prediction (the target gets no gradient): ``forward``'s
+    scalar or, ``rows``, ``per_item``'s [B] with a cotangent per row.  Backward, per resolution: the cotangent coefficients
+    [g / (nres sqrt(l0) sqrt(l1)) or 0, g / (nres count)] of the sums l (ias_mrstft_coef; rows: a pair per row with the row's
+    cotangent folded in, ias_mrstft_coef_rows)
+    (d (sqrt(l0) / sqrt(l1)) / dV = (V - T) / (sqrt(l0) sqrt(l1));  d (l2 / count) / dV = sign(V - T) / (V count)),
+    then the chunk spans of d loss / d (windowed frames), overlap-added inside the kernel, and one ias_stft_grad_combine for
+    all resolutions; where a resolution's shape has no chunk plan (or ``fused_combine`` is off) every resolution's own
+    d loss / d audio instead, summed in resolution order."""
 
     @staticmethod
-    def forward(ctx, x, module, *targets):
+    def forward(ctx, x, module, rows, *targets):
         a = STFTPlan._audio2d(x)
-        loss, saved = module._forward(a, targets)
-        ctx.module, ctx.shape = module, x.shape
-        ctx.save_for_backward(a, *[t for pair in saved for t in pair])
-        return loss
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        a, *rest = ctx.saved_tensors
-        module = ctx.module
-        lib = _lib.load()
-        B, T = a.shape
-        nres = len(module.plans)
-        g32 = g_loss.to(torch.float32).reshape(()).contiguous()
-        cur = torch.cuda.current_stream(a.device)
-        streams = module._streams(a.device) if module.parallel else None
-        eps = float(module.eps)
-        # chunk plans of the fused overlap-add (csrc/spectral_kernels.hip, SPAN kernels); any unsupported shape -> the
-        # per-resolution path (frame tensor / spans + one combine each, summed with torch)
-        plans = []
-        for plan in module.plans:
-            hp = (ctypes.c_int * 3)()
-            if module.fused_combine and lib.ias_stft_grad_span_plan(B, T, plan.n_fft, plan.hop_length, 0, plan.n_out, hp) == 0:
-                plans.append((hp[0], hp[1], hp[2]))
-        if len(plans) == nres and nres <= 8:
-            spans = []
-            for i, plan in enumerate(module.plans):
-                tgt, s = rest[2 * i], rest[2 * i + 1]
-                if streams is not None:
-                    streams[i].wait_stream(cur)
-                with torch.cuda.stream(streams[i] if streams is not None else cur):
-                    spans.append(_mrstft_plan_spans(lib, plan, a, tgt, s, g32, nres, eps, plans[i], cur))
-            if streams is not None:
-                for st in streams[:nres]:
-                    cur.wait_stream(st)
-            g_total = torch.empty_like(a)
-            ptrs = (ctypes.c_void_p * nres)(*[sp.data_ptr() for sp in spans])
-            flat = []
-            for plan, (G, cper, L) in zip(module.plans, plans):
-                flat += [plan.n_fft, plan.hop_length, G, cper, L]
-            _lib.check(lib.ias_stft_grad_combine(ptrs, (ctypes.c_int * len(flat))(*flat), nres, None, _lib.ptr(g_total),
-                                                 B, T, _lib.stream()), "ias_stft_grad_combine")
-            return (g_total.reshape(ctx.shape), None) + (None,) * nres
-        grads = []
-        for i, plan in enumerate(module.plans):
-            tgt, s = rest[2 * i], rest[2 * i + 1]
-            if streams is not None:
-                streams[i].wait_stream(cur)
-            with torch.cuda.stream(streams[i] if streams is not None else cur):
-                grads.append(_mrstft_plan_backward(lib, plan, a, tgt, s, g32, nres, eps, cur))
-        g_total = None
-        for i, g_audio in enumerate(grads):      # joined in a fixed order
-            if streams is not None:
-                cur.wait_stream(streams[i])
-            g_total = g_audio if g_total is None else g_total + g_audio
-        return (g_total.reshape(ctx.shape), None) + (None,) * len(module.plans)
-
-
-class _MRSTFTRowsFn(torch.autograd.Function):
-    """MultiResolutionSTFTLoss.per_item with the HIP adjoint w.r.t. the prediction for a cotangent per row: per resolution
-    the coefficient pairs of every row (ias_mrstft_coef_rows, the row's cotangent folded in), then the span kernels with one
-    ias_stft_grad_combine for all resolutions, or, where a resolution's shape has no span plan, the per-resolution path
-    summed in resolution order (as _MRSTFTFn.backward)."""
-
-    @staticmethod
-    def forward(ctx, x, module, *targets):
-        a = STFTPlan._audio2d(x)
-        out, sums = module._forward_rows(a, targets)
-        ctx.module, ctx.shape = module, x.shape
+        out, sums = module._forward(a, targets, rows)
+        ctx.module, ctx.rows, ctx.shape = module, rows, x.shape
         ctx.save_for_backward(a, *targets, *sums)
         return out
 
     @staticmethod
-    def backward(ctx, g_rows):
-        module = ctx.module
+    def backward(ctx, g):
+        module, rows = ctx.module, ctx.rows
         nres = len(module.plans)
         a, rest = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         targets, sums = rest[:nres], rest[nres:]
         lib = _lib.load()
         B, T = a.shape
-        g = g_rows.to(torch.float32).reshape(B).contiguous()
-        cur = torch.cuda.current_stream(a.device)
-        streams = module._streams(a.device) if module.parallel else None
+        g32 = g.to(torch.float32).reshape(B if rows else ()).contiguous()
         eps = float(module.eps)
-        plans = []
+        # chunk plans of the fused overlap-add (csrc/spectral_kernels.hip, SPAN kernels)
+        chunk_plans = []
         for plan in module.plans:
             hp = (ctypes.c_int * 3)()
-            if lib.ias_stft_grad_span_plan(B, T, plan.n_fft, plan.hop_length, 0, plan.n_out, hp) == 0:
-                plans.append((hp[0], hp[1], hp[2]))
-        spans_path = len(plans) == nres and nres <= 8
-        parts = []
-        for i, plan in enumerate(module.plans):
-            if streams is not None:
-                streams[i].wait_stream(cur)
-            with torch.cuda.stream(streams[i] if streams is not None else cur):
-                side = torch.cuda.current_stream(a.device)
-                g.record_stream(side)
-                coef = torch.empty((B, 2), dtype=torch.float64, device=a.device)
-                _lib.check(lib.ias_mrstft_coef_rows(_lib.ptr(sums[i]), _lib.ptr(g), float(targets[i][0].numel()), nres, B,
+            if module.fused_combine and lib.ias_stft_grad_span_plan(B, T, plan.n_fft, plan.hop_length, 0, plan.n_out, hp) == 0:
+                chunk_plans.append((hp[0], hp[1], hp[2]))
+        fused = len(chunk_plans) == nres and nres <= 8
+
+        def part(k, plan):
+            tgt = targets[k]
+            g32.record_stream(torch.cuda.current_stream(a.device))
+            coef = torch.empty((B, 2) if rows else 2, dtype=torch.float64, device=a.device)
+            if rows:
+                _lib.check(lib.ias_mrstft_coef_rows(_lib.ptr(sums[k]), _lib.ptr(g32), float(tgt[0].numel()), nres, B,
                                                     _lib.ptr(coef), _lib.stream()), "ias_mrstft_coef_rows")
-                if spans_path:
-                    G, cper, L = plans[i]
-                    out = torch.empty(B * cper * L, dtype=torch.float32, device=a.device)
-                    hp = (ctypes.c_int * 3)()
-                    _lib.check(lib.ias_stft_grad_spans_mrstft_rows(
-                        _lib.ptr(a), _lib.ptr(plan.tables), plan.n_out, _lib.ptr(targets[i]), _lib.ptr(coef), _lib.ptr(out),
-                        B, T, plan.n_fft, plan.hop_length, eps, hp, _lib.stream()), "ias_stft_grad_spans_mrstft_rows")
-                    assert (hp[0], hp[1], hp[2]) == plans[i]
+            else:
+                _lib.check(lib.ias_mrstft_coef(_lib.ptr(sums[k]), _lib.ptr(g32), float(tgt.numel()), nres, _lib.ptr(coef),
+                                               _lib.stream()), "ias_mrstft_coef")
+            if fused:
+                G, cper, L = chunk_plans[k]
+                out = torch.empty(B * cper * L, dtype=torch.float32, device=a.device)
+                hp = (ctypes.c_int * 3)()
+                if rows:
+                    st = lib.ias_stft_grad_spans_mrstft_rows(
+                        _lib.ptr(a), _lib.ptr(plan.tables), plan.n_out, _lib.ptr(tgt), _lib.ptr(coef), _lib.ptr(out), B, T,
+                        plan.n_fft, plan.hop_length, eps, hp, _lib.stream())
                 else:
-                    frame_grad = torch.empty((B, plan.num_frames(T), plan.n_fft), dtype=torch.float32, device=a.device)
-                    out = torch.empty_like(a)
-                    _lib.check(lib.ias_stft_loss_backward_mrstft_rows(
-                        _lib.ptr(a), _lib.ptr(plan.window), _lib.ptr(plan.tables), _lib.ptr(targets[i]), _lib.ptr(coef),
-                        _lib.ptr(frame_grad), _lib.ptr(out), B, T, plan.n_fft, plan.hop_length, plan.n_out, eps,
-                        _lib.stream()), "ias_stft_loss_backward_mrstft_rows")
-                out.record_stream(cur)
-                parts.append(out)
-        if streams is not None:
-            for st in streams[:nres]:
-                cur.wait_stream(st)
-        if spans_path:
+                    st = lib.ias_stft_grad_spans(
+                        _lib.ptr(a), _lib.ptr(plan.tables), None, None, None, None, 0, plan.n_out, _lib.ptr(tgt),
+                        _lib.ptr(coef), _lib.ptr(out), B, T, plan.n_fft, plan.hop_length, 1, LOSS_MRSTFT, 0.0, eps, hp,
+                        _lib.stream())
+                _lib.check(st, "ias_stft_grad_spans_mrstft_rows" if rows else "ias_stft_grad_spans")
+                assert (hp[0], hp[1], hp[2]) == chunk_plans[k]
+                return out
+            frame_grad = torch.empty((B, plan.num_frames(T), plan.n_fft), dtype=torch.float32, device=a.device)
+            out = torch.empty_like(a)
+            if rows:
+                st = lib.ias_stft_loss_backward_mrstft_rows(
+                    _lib.ptr(a), _lib.ptr(plan.window), _lib.ptr(plan.tables), _lib.ptr(tgt), _lib.ptr(coef),
+                    _lib.ptr(frame_grad), _lib.ptr(out), B, T, plan.n_fft, plan.hop_length, plan.n_out, eps, _lib.stream())
+            else:
+                st = lib.ias_stft_loss_backward(
+                    _lib.ptr(a), _lib.ptr(plan.window), _lib.ptr(plan.tables), None, None, None, None, 0, _lib.ptr(tgt),
+                    None, _lib.ptr(coef), _lib.ptr(frame_grad), _lib.ptr(out), B, T, plan.n_fft, plan.hop_length,
+                    plan.n_out, 1, LOSS_MRSTFT, 0.0, eps, _lib.stream())
+            _lib.check(st, "ias_stft_loss_backward_mrstft_rows" if rows else "ias_stft_loss_backward")
+            return out
+
+        parts = module._each_resolution(a.device, part)
+        if fused:
             g_total = torch.empty_like(a)
             ptrs = (ctypes.c_void_p * nres)(*[sp.data_ptr() for sp in parts])
             flat = []
-            for plan, (G, cper, L) in zip(module.plans, plans):
+            for plan, (G, cper, L) in zip(module.plans, chunk_plans):
                 flat += [plan.n_fft, plan.hop_length, G, cper, L]
             _lib.check(lib.ias_stft_grad_combine(ptrs, (ctypes.c_int * len(flat))(*flat), nres, None, _lib.ptr(g_total),
                                                  B, T, _lib.stream()), "ias_stft_grad_combine")
         else:
             g_total = parts[0]
-            for p in parts[1:]:                  # joined in a fixed order
+            for p in parts[1:]:                  # in resolution order
                 g_total = g_total + p
-        return (g_total.reshape(ctx.shape), None) + (None,) * nres
-
-
-def _mrstft_coef(lib, s, g32, count, nres, device):
-    """[g / (nres sqrt(l0) sqrt(l1)) or 0, g / (nres count)]: the cotangent coefficients of one resolution
-    (d (sqrt(l0) / sqrt(l1)) / dV = (V - T) / (sqrt(l0) sqrt(l1));  d (l2 / count) / dV = sign(V - T) / (V count))."""
-    coef = torch.empty(2, dtype=torch.float64, device=device)
-    _lib.check(lib.ias_mrstft_coef(_lib.ptr(s), _lib.ptr(g32), float(count), nres, _lib.ptr(coef), _lib.stream()),
-               "ias_mrstft_coef")
-    return coef
-
-
-def _mrstft_plan_spans(lib, plan, a, tgt, s, g32, nres, eps, chunk_plan, consumer_stream):
-    """One resolution's chunk spans of d loss / d (windowed frames), overlap-added inside the kernel (on the current
-    stream; the result is handed to ``consumer_stream``, where ``ias_stft_grad_combine`` finishes all resolutions)."""
-    B, T = a.shape
-    g32.record_stream(torch.cuda.current_stream(a.device))
-    coef = _mrstft_coef(lib, s, g32, tgt.numel(), nres, a.device)
-    G, cper, L = chunk_plan
-    spans = torch.empty(B * cper * L, dtype=torch.float32, device=a.device)
-    hp = (ctypes.c_int * 3)()
-    st = lib.ias_stft_grad_spans(_lib.ptr(a), _lib.ptr(plan.tables), None, None, None, None, 0, plan.n_out, _lib.ptr(tgt),
-                                 _lib.ptr(coef), _lib.ptr(spans), B, T, plan.n_fft, plan.hop_length, 1, LOSS_MRSTFT, 0.0,
-                                 eps, hp, _lib.stream())
-    _lib.check(st, "ias_stft_grad_spans")
-    assert (hp[0], hp[1], hp[2]) == chunk_plan
-    spans.record_stream(consumer_stream)
-    return spans
-
-
-def _mrstft_plan_backward(lib, plan, a, tgt, s, g32, nres, eps, consumer_stream):
-    """One resolution's d loss / d audio (on the current stream; the result is handed to ``consumer_stream``)."""
-    B, T = a.shape
-    g32.record_stream(torch.cuda.current_stream(a.device))
-    coef = _mrstft_coef(lib, s, g32, tgt.numel(), nres, a.device)
-    frame_grad = torch.empty((B, plan.num_frames(T), plan.n_fft), dtype=torch.float32, device=a.device)
-    g_audio = torch.empty_like(a)
-    st = lib.ias_stft_loss_backward(_lib.ptr(a), _lib.ptr(plan.window), _lib.ptr(plan.tables), None, None, None,
-                                    None, 0, _lib.ptr(tgt), None, _lib.ptr(coef), _lib.ptr(frame_grad),
-                                    _lib.ptr(g_audio), B, T, plan.n_fft, plan.hop_length, plan.n_out, 1, LOSS_MRSTFT,
-                                    0.0, eps, _lib.stream())
-    _lib.check(st, "ias_stft_loss_backward")
-    g_audio.record_stream(consumer_stream)
-    return g_audio
+        return (g_total.reshape(ctx.shape), None, None) + (None,) * nres
 
 
 class ParallelLossSum(nn.Module):
