@@ -40,8 +40,9 @@ long long ias_voice_workspace_bytes(int B, int T, int Tc);
 /* Control-rate pass only: params01 [B,78] in [0,1] (registration order, voice_spec.py) ->
  * ctrl [B,5,Tc] (mod-matrix outputs) and vconst [B] x 64 bytes (IasVoiceConst).  env [B,8,Tc] is
  * scratch that receives the six envelopes (adsr_1, adsr_2, lfo_1_amp, lfo_2_amp, lfo_1_rate, lfo_2_rate)
- * and the two LFO outputs. */
-int ias_voice_control(const float* params01, float* ctrl, void* vconst, float* env, int B, int Tc,
+ * and the two LFO outputs.  dbg (may be NULL) receives the intermediates [B,10,Tc]: rows 0-5 the envelopes,
+ * 6-7 the LFO phases, 8-9 the LFO outputs. */
+int ias_voice_control(const float* params01, float* ctrl, void* vconst, float* env, float* dbg, int B, int Tc,
                       int control_rate, void* stream);
 
 /* ias_voice_control into the ctrl / vconst / env regions of an ias_voice_render workspace (workspace_bytes >=
@@ -49,11 +50,6 @@ int ias_voice_control(const float* params01, float* ctrl, void* vconst, float* e
  * split into separately launchable pieces (pipelined schedules).  The workspace layout is private to the library. */
 int ias_voice_control_ws(const float* params01, void* workspace, long long workspace_bytes, int B, int T, int Tc,
                          int control_rate, void* stream);
-
-/* Same as ias_voice_control plus the intermediates dbg [B,10,Tc]: rows 0-5 the envelopes,
- * 6-7 the LFO phases, 8-9 the LFO outputs. */
-int ias_voice_control_debug(const float* params01, float* ctrl, void* vconst, float* env, float* dbg, int B,
-                            int Tc, int control_rate, void* stream);
 
 /* Voice.output(): params01 [B,78], noise [B,T] (the fixed Noise(seed=13) buffer) -> audio [B,T].
  * normalize != 0 applies torchsynth's normalize_if_clipping (row / max(|row|) when the max > 1).
@@ -112,35 +108,28 @@ int ias_pqmf_out_len(int T, int N, int K);
  * g_mixed [B,T] = d loss / d (un-normalised mix).  Scratch: planes [B, ias_voice_grad_nplanes(), T] fp32,
  * tile_sums [B, ias_voice_grad_tiles(T), 2] fp64.  Outputs: g_ctrl [B,5,Tc] fp32 = d loss / d ctrl;
  * partials [B, ias_voice_grad_tiles(T), ias_voice_grad_nscalars()] fp64, whose sum over tiles is d loss / d of the
- * per-voice constants f0_1 depth_1 phi_1 f0_2 depth_2 phi_2 kpart shape gain lvl0 lvl1 lvl2. */
-int ias_voice_grad_tiles(int T);
-int ias_voice_grad_nscalars(void);
-int ias_voice_grad_nplanes(void);
-int ias_voice_backward(const float* ctrl, const void* vconst, const float* noise, const float* g_mixed,
-                       float* planes, double* tile_sums, double* partials, float* g_ctrl, int B, int T, int Tc,
-                       int sample_rate, void* stream);
-/* The same behind torchsynth's normalize_if_clipping (audio = mix / peak on rows with peak = max |mix| > 1): g_audio is
+ * per-voice constants f0_1 depth_1 phi_1 f0_2 depth_2 phi_2 kpart shape gain lvl0 lvl1 lvl2; g_scal
+ * [B, ias_voice_grad_nscalars()] fp64 (may be NULL) = partials summed over the tiles (in tile order) -- the gradient of
+ * the per-voice constants -- instead of leaving that sum to the caller.
+ * Behind torchsynth's normalize_if_clipping (audio = mix / peak on rows with peak = max |mix| > 1) g_mixed is
  * the cotangent of the NORMALISED audio [B,T]; ias_voice_norm_backward turns it, the audio and the row peaks
  * (ias_voice_read_peaks) into rownorm [B][4] = {divisor, index t* of the peak sample as int bits (-1: none), correction
  * -sign(audio[t*]) sum_t g[t] audio[t] / peak, 0} with two launches (scratch: B * ias_voice_norm_scratch_len(T)
- * doubles); ias_voice_backward_norm applies g / divisor (+ correction at t*) as it reads g_audio.  rownorm NULL =
- * ias_voice_backward.  Replaces the 14 elementwise / reduce / gather / scatter launches of the torch expression. */
+ * doubles); ias_voice_backward applies g / divisor (+ correction at t*) as it reads g_mixed.  rownorm NULL = g_mixed is
+ * the cotangent of the mix itself.  Replaces the 14 elementwise / reduce / gather / scatter launches of the torch
+ * expression.
+ * stage -1: everything.  0 / 1: in two stages on the same buffers: stage 0 = the phase increments and their tile sums
+ * from the control signals (no cotangent: g_mixed, rownorm, noise, partials, g_ctrl, g_scal may be NULL), stage 1 =
+ * everything else.  Any other stage: IAS_ERR_ARG. */
+int ias_voice_grad_tiles(int T);
+int ias_voice_grad_nscalars(void);
+int ias_voice_grad_nplanes(void);
 long long ias_voice_norm_scratch_len(int T);
 int ias_voice_norm_backward(const float* g_audio, const float* audio, const float* peaks, double* scratch,
                             float* rownorm, int B, int T, void* stream);
-int ias_voice_backward_norm(const float* ctrl, const void* vconst, const float* noise, const float* g_audio,
-                            const float* rownorm, float* planes, double* tile_sums, double* partials, float* g_ctrl,
-                            int B, int T, int Tc, int sample_rate, void* stream);
-/* ias_voice_backward_norm that also leaves g_scal [B, ias_voice_grad_nscalars()] fp64 = partials summed over the tiles (in
- * tile order) -- the gradient of the per-voice constants -- instead of leaving that sum to the caller. */
-int ias_voice_backward_sums(const float* ctrl, const void* vconst, const float* noise, const float* g_mixed,
-                            const float* rownorm, float* planes, double* tile_sums, double* partials, float* g_ctrl,
-                            double* g_scal, int B, int T, int Tc, int sample_rate, void* stream);
-/* In two stages on the same buffers: stage 0 = the phase increments and their tile sums from the control signals (no
- * cotangent: g_mixed, rownorm, noise, partials, g_ctrl, g_scal may be NULL), stage 1 = everything else. */
-int ias_voice_backward_sums_stage(int stage, const float* ctrl, const void* vconst, const float* noise, const float* g_mixed,
-                                  const float* rownorm, float* planes, double* tile_sums, double* partials, float* g_ctrl,
-                                  double* g_scal, int B, int T, int Tc, int sample_rate, void* stream);
+int ias_voice_backward(int stage, const float* ctrl, const void* vconst, const float* noise, const float* g_mixed,
+                       const float* rownorm, float* planes, double* tile_sums, double* partials, float* g_ctrl,
+                       double* g_scal, int B, int T, int Tc, int sample_rate, void* stream);
 
 /* Control-rate half of the same backward: params01 [B,78], g_ctrl [B,5,Tc] fp32 and g_scal [B,12] fp64 (g_ctrl of
  * ias_voice_backward and the sum over tiles of its partials) -> g_params01 [B,78] fp32.  One launch instead of the
@@ -149,17 +138,15 @@ int ias_voice_backward_sums_stage(int stage, const float* ctrl, const void* vcon
 int ias_voice_control_backward(const float* params01, const float* g_ctrl, const double* g_scal, float* g_params01,
                                int B, int Tc, int control_rate, void* stream);
 /* The same in three launches (round 3): the six-envelope phase -- 60 % of the fp64 pow / log work -- on 6 x B workgroups
- * instead of B.  workspace: ias_voice_control_backward_ws_bytes(B, Tc) bytes of device memory, 16-byte aligned. */
+ * instead of B.  workspace: ias_voice_control_backward_ws_bytes(B, Tc) bytes of device memory, 16-byte aligned.
+ * stage -1: everything.  0 / 1: in two stages on the same workspace: stage 0 = the part that does not see the cotangent
+ * (the envelope values, parameters only; g_ctrl, g_scal, g_params01 may be NULL) -- a caller that knows at render time
+ * that a backward will follow can run it beside the loss computation on another stream; stage 1 = the rest.  Any other
+ * stage: IAS_ERR_ARG. */
 long long ias_voice_control_backward_ws_bytes(int B, int Tc);
-int ias_voice_control_backward_ws(const float* params01, const float* g_ctrl, const double* g_scal, float* g_params01,
-                                  void* workspace, long long workspace_bytes, int B, int Tc, int control_rate,
-                                  void* stream);
-/* The same in two stages on the same workspace: stage 0 = the part that does not see the cotangent (the envelope values,
- * parameters only; g_ctrl, g_scal, g_params01 may be NULL) -- a caller that knows at render time that a backward will
- * follow can run it beside the loss computation on another stream; stage 1 = the rest. */
-int ias_voice_control_backward_ws_stage(int stage, const float* params01, const float* g_ctrl, const double* g_scal,
-                                        float* g_params01, void* workspace, long long workspace_bytes, int B, int Tc,
-                                        int control_rate, void* stream);
+int ias_voice_control_backward_ws(int stage, const float* params01, const float* g_ctrl, const double* g_scal,
+                                  float* g_params01, void* workspace, long long workspace_bytes, int B, int Tc,
+                                  int control_rate, void* stream);
 
 /* Transposed, zero-padded tap table: ias_pqmf_packed_taps_len(N, K) floats -- the fast kernel's layout for N = 3, 4
  * with K = 63, the wide kernel's [K][8|16|32|64] layout for other N <= 64 with K <= 255, 0 otherwise (generic
@@ -191,14 +178,12 @@ int ias_pqmf_build_modtab(const float* H_host, int N, int K, float* out_host);
 int ias_pqmf_analysis(const float* x, const float* H, const float* packed, const float* modtab, float* z, const float* mean,
                       const float* stdv, const float* rowpeak, int B, int T, int N, int K, void* stream);
 
-/* synthesis: z [B,N,L], G [N,K] (= buffer G[1,N,K]) -> out [B, L*N] (= [B,1,L*N])   (pqmf.py:52-55). */
+/* synthesis: z [B,N,L], G [N,K] (= buffer G[1,N,K]) -> out [B, T_out], T_out <= L * N: the first T_out samples of every
+ * row of [B, L*N] (= [B,1,L*N]), contiguous   (pqmf.py:52-55). */
 /* packed: ias_pqmf_pack_synth_taps table of G (ias_pqmf_synth_taps_len floats; wide kernel for N <= 64, K <= 255),
  * or NULL (generic kernel, several times slower). */
 int ias_pqmf_synth_taps_len(int N, int K);
 int ias_pqmf_pack_synth_taps(const float* G, float* packed, int N, int K, void* stream);
-int ias_pqmf_synthesis(const float* z, const float* G, const float* packed, float* out, int B, int L, int N, int K,
-                       void* stream);
-/* The same into out [B, T_out], T_out <= L * N: the first T_out samples of every row, contiguous. */
 int ias_pqmf_synthesis_t(const float* z, const float* G, const float* packed, float* out, int B, int L, int N, int K,
                          int T_out, void* stream);
 
@@ -434,36 +419,25 @@ int ias_reduce_partials(const double* partials, long long n, double* sums, doubl
 /* Workspace bytes for ias_vicreg_loss (bf16 transposed centred copies, column stats, partials). */
 long long ias_vicreg_workspace_bytes(int B, int D);
 
-/* Byte offset inside that workspace of colstats [4][D] fp32 (mean_x, mean_y, sum (x-mean)^2, same for y),
- * valid after ias_vicreg_loss. */
-long long ias_vicreg_colstats_offset(int B, int D);
-
 /* x, y [B,D] fp32 -> out[4] = (loss, repr_loss, std_loss, cov_loss).  cfg_batch: the CONFIGURED batch
  * size whose (cfg_batch - 1) divides the covariance (vicreg.py:47-48 reads it from cfg, not from x). */
 int ias_vicreg_loss(const float* x, const float* y, float* out, void* workspace, long long workspace_bytes,
                     int B, int D, int cfg_batch, float sim_coeff, float std_coeff, float cov_coeff, void* stream);
 
-/* Backward of ias_vicreg_loss (the reference gets it from autograd through vicreg.py:35-58): gcoef [4] device floats,
- * the cotangents of (loss, repr_loss, std_loss, cov_loss) -> gx, gy [B,D] fp32.  Same workspace as the forward call,
- * untouched in between (it holds the column statistics and the centred bf16 copies); D % 8 == 0.  Closed form with
- * the B x B Gram (never a D x D matrix); both matrix products on the bf16 matrix cores, fp32 accumulate. */
-int ias_vicreg_backward(const float* x, const float* y, const float* gcoef, float* gx, float* gy, void* workspace,
-                        long long workspace_bytes, int B, int D, int cfg_batch, float sim_coeff, float std_coeff,
-                        float cov_coeff, void* stream);
-
-/* The same pair for x, y (and gx, gy) that are COLUMN BLOCKS of wider row-major matrices: row strides ld / ldg in floats
+/* The same loss for x, y that are COLUMN BLOCKS of wider row-major matrices: row strides ld / ldg in floats
  * (>= D; with ld != D or ldg != D: multiples of 4 and 16-byte aligned base pointers).  This is how the global-batch loss
  * of the gather the reference keeps commented out (vicreg.py:38-39 with FullGatherLayer :79-95) runs without copies:
  * ONE all-gather of cat(x, y, dim=1) lands in a [W B_l, 2 D] buffer, x = buf[:, :D], y = buf[:, D:] are consumed in
  * place, and the two gradient blocks are written straight into the [W B_l, 2 D] cotangent the backward reduce-scatters. */
 int ias_vicreg_loss_ld(const float* x, const float* y, long long ld, float* out, void* workspace, long long workspace_bytes,
                        int B, int D, int cfg_batch, float sim_coeff, float std_coeff, float cov_coeff, void* stream);
-int ias_vicreg_backward_ld(const float* x, const float* y, long long ld, const float* gcoef, float* gx, float* gy,
-                           long long ldg, void* workspace, long long workspace_bytes, int B, int D, int cfg_batch,
-                           float sim_coeff, float std_coeff, float cov_coeff, void* stream);
 
-/* ias_vicreg_backward_ld with the four cotangents as separate device floats, any of them NULL (= zero): autograd hands the
- * outputs that were not differentiated over as None, and packing four scalars into gcoef costs a kernel per step. */
+/* Backward of ias_vicreg_loss[_ld] (the reference gets it from autograd through vicreg.py:35-58): the cotangents of
+ * (loss, repr_loss, std_loss, cov_loss) -> gx, gy [B,D] fp32 with row stride ldg.  Same workspace as the forward call,
+ * untouched in between (it holds the column statistics and the centred bf16 copies); D % 8 == 0.  Closed form with
+ * the B x B Gram (never a D x D matrix); both matrix products on the bf16 matrix cores, fp32 accumulate.
+ * The four cotangents are separate device floats, any of them NULL (= zero): autograd hands the
+ * outputs that were not differentiated over as None, and packing four scalars costs a kernel per step. */
 int ias_vicreg_backward4_ld(const float* x, const float* y, long long ld, const float* g_loss, const float* g_repr,
                             const float* g_std, const float* g_cov, float* gx, float* gy, long long ldg, void* workspace,
                             long long workspace_bytes, int B, int D, int cfg_batch, float sim_coeff, float std_coeff,
@@ -488,7 +462,6 @@ int ias_conv_out_size(int n, int K, int S);
 int ias_dwconv_forward(const float* x, const float* w, float* out, int B, int C, int H, int W, int K, int S, void* stream);
 int ias_dwconv_backward_data(const float* g, const float* w, float* gx, int B, int C, int H, int W, int K, int S,
                              void* stream);
-long long ias_dwconv_weight_scratch(int B, int C, int K);     /* floats: upper bound for any plane size */
 long long ias_dwconv_weight_scratch_hw(int B, int C, int H, int W, int K, int S);   /* floats, for this plane size */
 int ias_dwconv_backward_weight(const float* x, const float* g, float* gw, float* scratch, int B, int C, int H, int W,
                                int K, int S, void* stream);

@@ -29,9 +29,8 @@ SYMBOLS = {
     "ias_stream_copy": (_I, [_P, _P, _LL, _P]),
     "ias_stamp": (_I, [_P, _P]),
     "ias_voice_workspace_bytes": (_LL, [_I, _I, _I]),
-    "ias_voice_control": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "ias_voice_control": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ias_voice_control_ws": (_I, [_P, _P, _LL, _I, _I, _I, _I, _P]),
-    "ias_voice_control_debug": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ias_voice_render": (_I, [_P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ias_voice_stage": (_I, [_I, _I, _P, _P, _P, _LL, _I, _I, _I, _I, _P]),
     "ias_voice_read_status": (_I, [_P, _P, _I, _I, _I, _P]),
@@ -44,16 +43,12 @@ SYMBOLS = {
     "ias_voice_grad_tiles": (_I, [_I]),
     "ias_voice_grad_nscalars": (_I, []),
     "ias_voice_grad_nplanes": (_I, []),
-    "ias_voice_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ias_voice_backward_norm": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ias_voice_backward_sums": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ias_voice_backward_sums_stage": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "ias_voice_backward": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "ias_voice_norm_scratch_len": (_LL, [_I]),
     "ias_voice_norm_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
     "ias_voice_control_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "ias_voice_control_backward_ws_bytes": (_LL, [_I, _I]),
-    "ias_voice_control_backward_ws": (_I, [_P, _P, _P, _P, _P, _LL, _I, _I, _I, _P]),
-    "ias_voice_control_backward_ws_stage": (_I, [_I, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P]),
+    "ias_voice_control_backward_ws": (_I, [_I, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P]),
     "ias_pqmf_out_len": (_I, [_I, _I, _I]),
     "ias_pqmf_packed_taps_len": (_I, [_I, _I]),
     "ias_pqmf_pack_taps": (_I, [_P, _P, _I, _I, _P]),
@@ -62,7 +57,6 @@ SYMBOLS = {
     "ias_pqmf_analysis": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "ias_pqmf_synth_taps_len": (_I, [_I, _I]),
     "ias_pqmf_pack_synth_taps": (_I, [_P, _P, _I, _I, _P]),
-    "ias_pqmf_synthesis": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "ias_pqmf_synthesis_t": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ias_stft_num_frames": (_I, [_I, _I, _I]),
     "ias_stft_partials_count": (_LL, [_I, _I, _I, _I, _I]),
@@ -106,17 +100,13 @@ SYMBOLS = {
     "ias_stft_grad_frames_mrstft_rows": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "ias_stft_grad_spans_mrstft_rows": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P]),
     "ias_vicreg_workspace_bytes": (_LL, [_I, _I]),
-    "ias_vicreg_colstats_offset": (_LL, [_I, _I]),
     "ias_vicreg_loss": (_I, [_P, _P, _P, _P, _LL, _I, _I, _I, _F, _F, _F, _P]),
-    "ias_vicreg_backward": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _F, _F, _F, _P]),
     "ias_vicreg_loss_ld": (_I, [_P, _P, _LL, _P, _P, _LL, _I, _I, _I, _F, _F, _F, _P]),
-    "ias_vicreg_backward_ld": (_I, [_P, _P, _LL, _P, _P, _P, _LL, _P, _LL, _I, _I, _I, _F, _F, _F, _P]),
     "ias_vicreg_backward4_ld": (_I, [_P, _P, _LL, _P, _P, _P, _P, _P, _P, _LL, _P, _LL, _I, _I, _I, _F, _F, _F, _P]),
     "ias_vicreg_stage": (_I, [_I, _P, _P, _P, _P, _LL, _I, _I, _I, _F, _F, _F, _P]),
     "ias_conv_out_size": (_I, [_I, _I, _I]),
     "ias_dwconv_forward": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ias_dwconv_backward_data": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "ias_dwconv_weight_scratch": (_LL, [_I, _I, _I]),
     "ias_dwconv_weight_scratch_hw": (_LL, [_I, _I, _I, _I, _I, _I]),
     "ias_dwconv_backward_weight": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ias_dwconv_backward_weight_partials": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -1102,18 +1102,14 @@ extern "C" int ias_dwconv_backward_data(const float* g, const float* w, float* g
 }
 
 // floats of scratch for ias_dwconv_backward_weight: one K x K partial per (b, c) plane and row tile (large planes are cut
-// into up to DW_MAX_TILES row tiles, one workgroup each); without the plane's size: the upper bound
-extern "C" long long ias_dwconv_weight_scratch(int B, int C, int K) {
-  if (B <= 0 || C <= 0 || K <= 0) return IAS_ERR_ARG;
-  return (long long)B * C * K * K * DW_MAX_TILES;
-}
+// into up to DW_MAX_TILES row tiles, one workgroup each)
 extern "C" long long ias_dwconv_weight_scratch_hw(int B, int C, int H, int W, int K, int S) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || !((K == 3 || K == 5) && (S == 1 || S == 2))) return IAS_ERR_ARG;
   const int Ho = ias_conv_out_size(H, K, S), Wo = ias_conv_out_size(W, K, S);
   return (long long)B * C * K * K * dw_tile_geometry(H, W, Ho, Wo, K, S, 1).ntiles;
 }
 
-// its gradient w.r.t. the weights: x [B,C,H,W], g [B,C,Ho,Wo] -> gw [C,1,K,K]; scratch: ias_dwconv_weight_scratch floats
+// its gradient w.r.t. the weights: x [B,C,H,W], g [B,C,Ho,Wo] -> gw [C,1,K,K]; scratch: ias_dwconv_weight_scratch_hw floats
 // gw == nullptr: the partial sums only -> *nrows rows of C K K floats in `scratch` (ias_dwconv_backward_weight_partials)
 static int dw_backward_weight(const float* x, const float* g, float* gw, float* scratch, int B, int C, int H, int W, int K,
                               int S, int* nrows, void* stream_) {

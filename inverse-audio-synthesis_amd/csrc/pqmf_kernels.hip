@@ -1315,17 +1315,10 @@ extern "C" int ias_pqmf_pack_synth_taps(const float* G, float* packed, int N, in
   return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
 }
 
-// z [B,N,L], G [N,K] (module buffer G[1,N,K]), out [B, L*N] (the reference's [B,1,L*N]).
+// z [B,N,L], G [N,K] (module buffer G[1,N,K]), out [B, T_out], T_out <= L * N: the first T_out samples of every row of
+// the reference's [B,1,L*N], contiguous (the adjoint of an analysis of T_out samples: no strided view of a [B, L * N]
+// result for the next kernel to walk).
 // packed: ias_pqmf_pack_synth_taps table of G (wide kernel), or NULL (generic one-lane-per-output kernel).
-// The same into out [B, T_out], T_out <= L * N: the first T_out samples of every row, contiguous (the adjoint of an
-// analysis of T_out samples: no strided view of a [B, L * N] result for the next kernel to walk).
-extern "C" int ias_pqmf_synthesis_t(const float* z, const float* G, const float* packed, float* out, int B, int L,
-                                    int N, int K, int T_out, void* stream_);
-extern "C" int ias_pqmf_synthesis(const float* z, const float* G, const float* packed, float* out, int B, int L,
-                                  int N, int K, void* stream_) {
-  if ((long long)L * N > 0x7fffffffLL) return IAS_ERR_ARG;
-  return ias_pqmf_synthesis_t(z, G, packed, out, B, L, N, K, L * N, stream_);
-}
 extern "C" int ias_pqmf_synthesis_t(const float* z, const float* G, const float* packed, float* out, int B, int L,
                                     int N, int K, int T_out, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;

@@ -953,7 +953,7 @@ extern "C" long long ias_vicreg_workspace_bytes(int B, int D) {
 
 // x, y [B,D] fp32 -> out[4] = (loss, repr_loss, std_loss, cov_loss).  cfg_batch = the configured batch
 // size whose (cfg_batch - 1) divides the covariance (vicreg.py:47-48).  After the call the workspace
-// holds colstats [4][D] (mean_x, mean_y, centred sum of squares x / y) at ias_vicreg_colstats_offset().
+// holds colstats [4][D] (mean_x, mean_y, centred sum of squares x / y) at VicregWs::colstats.
 // stage < 0: the whole loss; 0: column pass (means, centred bf16 transposes, MSE / hinge partials); 1: the Gram
 // kernel(s) on the matrix cores; 2: the final reduction.  Stages run on a workspace the earlier stages have filled
 // (bench.py times stage 1 alone with HIP events for the MFMA roofline).
@@ -1630,35 +1630,14 @@ static int vicreg_backward_ld(const float* x, const float* y, long long ld, cons
   return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
 }
 
-extern "C" int ias_vicreg_backward(const float* x, const float* y, const float* gcoef, float* gx, float* gy, void* workspace,
-                                   long long workspace_bytes, int B, int D, int cfg_batch, float sim_coeff, float std_coeff,
-                                   float cov_coeff, void* stream_) {
-  if (!gcoef) return IAS_ERR_ARG;
-  return vicreg_backward_ld(x, y, D, VcCot{{gcoef, gcoef + 1, gcoef + 2, gcoef + 3}}, gx, gy, D, workspace, workspace_bytes, B, D, cfg_batch, sim_coeff, std_coeff,
-                            cov_coeff, stream_);
-}
-
-// Backward of ias_vicreg_loss_ld: x, y with row stride ld, gx, gy WRITTEN with row stride ldg (the two column blocks of
-// the [W B_l, 2 D] cotangent that FullGatherLayer's backward reduce-scatters: no split / cat copies either way).
-extern "C" int ias_vicreg_backward_ld(const float* x, const float* y, long long ld, const float* gcoef, float* gx, float* gy,
-                                      long long ldg, void* workspace, long long workspace_bytes, int B, int D, int cfg_batch,
-                                      float sim_coeff, float std_coeff, float cov_coeff, void* stream_) {
-  if (!gcoef) return IAS_ERR_ARG;
-  return vicreg_backward_ld(x, y, ld, VcCot{{gcoef, gcoef + 1, gcoef + 2, gcoef + 3}}, gx, gy, ldg, workspace, workspace_bytes, B, D, cfg_batch, sim_coeff, std_coeff,
-                            cov_coeff, stream_);
-}
-
-// The same backward with the four cotangents as separate device floats, any of them null (= zero): what autograd hands
-// over when only some of the four outputs were differentiated -- no packing kernel in front.
+// The backward with the four cotangents as separate device floats, any of them null (= zero): what autograd hands
+// over when only some of the four outputs were differentiated -- no packing kernel in front.  x, y with row stride ld,
+// gx, gy WRITTEN with row stride ldg (the two column blocks of the [W B_l, 2 D] cotangent that FullGatherLayer's backward
+// reduce-scatters: no split / cat copies either way).
 extern "C" int ias_vicreg_backward4_ld(const float* x, const float* y, long long ld, const float* g_loss, const float* g_repr,
                                        const float* g_std, const float* g_cov, float* gx, float* gy, long long ldg,
                                        void* workspace, long long workspace_bytes, int B, int D, int cfg_batch,
                                        float sim_coeff, float std_coeff, float cov_coeff, void* stream_) {
   return vicreg_backward_ld(x, y, ld, VcCot{{g_loss, g_repr, g_std, g_cov}}, gx, gy, ldg, workspace, workspace_bytes, B, D,
                             cfg_batch, sim_coeff, std_coeff, cov_coeff, stream_);
-}
-
-extern "C" long long ias_vicreg_colstats_offset(int B, int D) {
-  if (B < 2 || D < 1) return IAS_ERR_ARG;
-  return (long long)vicreg_ws(B, D).colstats;
 }

@@ -551,27 +551,12 @@ extern "C" long long ias_voice_control_backward_ws_bytes(int B, int Tc) {
   if (B <= 0 || Tc <= 1) return IAS_ERR_ARG;
   return (long long)sizeof(float) * B * 6 * Tc + (long long)sizeof(double) * B * (2 * 78 + 40 + 6 * (long long)Tc) + 64;
 }
-static int voice_control_backward_stage(int stage, const float* params01, const float* g_ctrl, const double* g_scal,
-                                        float* g_params01, void* workspace, long long workspace_bytes, int B, int Tc,
-                                        int control_rate, void* stream_);
-extern "C" int ias_voice_control_backward_ws(const float* params01, const float* g_ctrl, const double* g_scal,
+// stage -1: everything; 0 / 1: in two stages on the same workspace: stage 0 = the envelope VALUES (voice_env_value_kernel:
+// parameters only, no cotangent; g_ctrl, g_scal, g_params01 may be NULL), stage 1 = the rest.
+extern "C" int ias_voice_control_backward_ws(int stage, const float* params01, const float* g_ctrl, const double* g_scal,
                                              float* g_params01, void* workspace, long long workspace_bytes, int B, int Tc,
                                              int control_rate, void* stream_) {
-  return voice_control_backward_stage(-1, params01, g_ctrl, g_scal, g_params01, workspace, workspace_bytes, B, Tc, control_rate,
-                                      stream_);
-}
-// In two stages on the same workspace: stage 0 = the envelope VALUES (voice_env_value_kernel: parameters only, no
-// cotangent; g_ctrl, g_scal, g_params01 may be NULL), stage 1 = the rest.
-extern "C" int ias_voice_control_backward_ws_stage(int stage, const float* params01, const float* g_ctrl, const double* g_scal,
-                                                   float* g_params01, void* workspace, long long workspace_bytes, int B,
-                                                   int Tc, int control_rate, void* stream_) {
-  if (stage != 0 && stage != 1) return IAS_ERR_ARG;
-  return voice_control_backward_stage(stage, params01, g_ctrl, g_scal, g_params01, workspace, workspace_bytes, B, Tc,
-                                      control_rate, stream_);
-}
-static int voice_control_backward_stage(int stage, const float* params01, const float* g_ctrl, const double* g_scal,
-                                        float* g_params01, void* workspace, long long workspace_bytes, int B, int Tc,
-                                        int control_rate, void* stream_) {
+  if (stage < -1 || stage > 1) return IAS_ERR_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   if (!params01 || !workspace || B <= 0 || B > 65535 || Tc <= 1 || control_rate <= 0) return IAS_ERR_ARG;
   if (stage != 0 && (!g_ctrl || !g_scal || !g_params01)) return IAS_ERR_ARG;

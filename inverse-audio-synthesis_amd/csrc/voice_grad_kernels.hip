@@ -950,28 +950,9 @@ extern "C" int ias_voice_grad_tiles(int T) { return T > 0 ? (T + GRAD_TILE - 1) 
 extern "C" int ias_voice_grad_nscalars(void) { return IAS_GRAD_NS; }
 extern "C" int ias_voice_grad_nplanes(void) { return IAS_GRAD_PLANES; }
 
-// ctrl [B,5,Tc], vconst [B] (64 B each): the outputs of ias_voice_control for the same parameters;
-// noise [B,T]; g_mixed [B,T] = d loss / d (un-normalised mix);
-// planes [B, ias_voice_grad_nplanes(), T] fp32 scratch; tile_sums [B, ntiles, 2] fp64 scratch;
-// partials [B, ntiles, ias_voice_grad_nscalars()] fp64 out (sum over tiles = gradient of the per-voice
-// constants in the order f0_1 depth_1 phi_1 f0_2 depth_2 phi_2 kpart shape gain lvl0 lvl1 lvl2);
-// g_ctrl [B,5,Tc] fp32 out.  ntiles = ias_voice_grad_tiles(T).
-extern "C" int ias_voice_backward_norm(const float* ctrl, const void* vconst, const float* noise, const float* g_mixed,
-                                       const float* rownorm, float* planes, double* tile_sums, double* partials,
-                                       float* g_ctrl, int B, int T, int Tc, int sample_rate, void* stream_);
-extern "C" int ias_voice_backward_sums(const float* ctrl, const void* vconst, const float* noise, const float* g_mixed,
-                                       const float* rownorm, float* planes, double* tile_sums, double* partials,
-                                       float* g_ctrl, double* g_scal, int B, int T, int Tc, int sample_rate, void* stream_);
-extern "C" int ias_voice_backward(const float* ctrl, const void* vconst, const float* noise, const float* g_mixed,
-                                  float* planes, double* tile_sums, double* partials, float* g_ctrl, int B, int T,
-                                  int Tc, int sample_rate, void* stream_) {
-  return ias_voice_backward_norm(ctrl, vconst, noise, g_mixed, nullptr, planes, tile_sums, partials, g_ctrl, B, T, Tc,
-                                 sample_rate, stream_);
-}
-
 // rownorm [B][4] from the cotangent g [B,T] of the NORMALISED audio [B,T] and the row peaks of the un-normalised mix
 // (ias_voice_read_peaks); scratch: ias_voice_norm_scratch_len(T) * B doubles.  Feed rownorm and g to
-// ias_voice_backward_norm: the division by the peak and the correction at the peak sample happen as g is read.
+// ias_voice_backward: the division by the peak and the correction at the peak sample happen as g is read.
 extern "C" long long ias_voice_norm_scratch_len(int T) {
   if (T <= 0) return IAS_ERR_ARG;
   return 2LL * ((T + NORM_TILE - 1) / NORM_TILE);
@@ -988,41 +969,25 @@ extern "C" int ias_voice_norm_backward(const float* g_audio, const float* audio,
   return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
 }
 
-// the same as ias_voice_backward with the cotangent of the normalised audio and its rownorm (NULL: g_mixed is the
-// cotangent of the mix itself)
-extern "C" int ias_voice_backward_norm(const float* ctrl, const void* vconst, const float* noise, const float* g_mixed,
-                                       const float* rownorm, float* planes, double* tile_sums, double* partials,
-                                       float* g_ctrl, int B, int T, int Tc, int sample_rate, void* stream_) {
-  return ias_voice_backward_sums(ctrl, vconst, noise, g_mixed, rownorm, planes, tile_sums, partials, g_ctrl, nullptr, B, T, Tc,
-                                 sample_rate, stream_);
-}
-// ... and g_scal [B, ias_voice_grad_nscalars()] fp64 (NULL: not wanted) = partials summed over the tiles, in tile order, by the
-// last launch
-static int voice_backward_stage(int stage, const float* ctrl, const void* vconst, const float* noise, const float* g_mixed,
-                                const float* rownorm, float* planes, double* tile_sums, double* partials, float* g_ctrl,
-                                double* g_scal, int B, int T, int Tc, int sample_rate, void* stream_);
-extern "C" int ias_voice_backward_sums(const float* ctrl, const void* vconst, const float* noise, const float* g_mixed,
-                                       const float* rownorm, float* planes, double* tile_sums, double* partials,
-                                       float* g_ctrl, double* g_scal, int B, int T, int Tc, int sample_rate, void* stream_) {
-  return voice_backward_stage(-1, ctrl, vconst, noise, g_mixed, rownorm, planes, tile_sums, partials, g_ctrl, g_scal, B, T, Tc,
-                              sample_rate, stream_);
-}
-// The same in two stages on the same buffers.  Stage 0 is the part that does not see the cotangent (the phase increments
-// and their tile sums from the control signals: voice_grad_inc_kernel) -- a caller that knows at render time that a
-// backward will follow can run it beside the loss computation, on another stream; stage 1 is everything else.
-// g_mixed, rownorm, partials, g_ctrl, g_scal may be NULL in stage 0.
-extern "C" int ias_voice_backward_sums_stage(int stage, const float* ctrl, const void* vconst, const float* noise,
-                                             const float* g_mixed, const float* rownorm, float* planes, double* tile_sums,
-                                             double* partials, float* g_ctrl, double* g_scal, int B, int T, int Tc,
-                                             int sample_rate, void* stream_) {
-  if (stage != 0 && stage != 1) return IAS_ERR_ARG;
-  return voice_backward_stage(stage, ctrl, vconst, noise, g_mixed, rownorm, planes, tile_sums, partials, g_ctrl, g_scal, B, T, Tc,
-                              sample_rate, stream_);
-}
-static int voice_backward_stage(int stage, const float* ctrl, const void* vconst, const float* noise, const float* g_mixed,
-                                const float* rownorm, float* planes, double* tile_sums, double* partials, float* g_ctrl,
-                                double* g_scal, int B, int T, int Tc, int sample_rate, void* stream_) {
+// ctrl [B,5,Tc], vconst [B] (64 B each): the outputs of ias_voice_control for the same parameters;
+// noise [B,T]; g_mixed [B,T] = d loss / d (un-normalised mix);
+// planes [B, ias_voice_grad_nplanes(), T] fp32 scratch; tile_sums [B, ntiles, 2] fp64 scratch;
+// partials [B, ntiles, ias_voice_grad_nscalars()] fp64 out (sum over tiles = gradient of the per-voice
+// constants in the order f0_1 depth_1 phi_1 f0_2 depth_2 phi_2 kpart shape gain lvl0 lvl1 lvl2);
+// g_ctrl [B,5,Tc] fp32 out.  ntiles = ias_voice_grad_tiles(T).
+// rownorm non-NULL: g_mixed is the cotangent of the normalised audio and rownorm its ias_voice_norm_backward (NULL:
+// g_mixed is the cotangent of the mix itself);
+// g_scal [B, ias_voice_grad_nscalars()] fp64 (NULL: not wanted) = partials summed over the tiles, in tile order, by the
+// last launch.
+// stage -1: everything; 0 / 1: the same in two stages on the same buffers.  Stage 0 is the part that does not see the
+// cotangent (the phase increments and their tile sums from the control signals: voice_grad_inc_kernel) -- a caller that
+// knows at render time that a backward will follow can run it beside the loss computation, on another stream; stage 1 is
+// everything else.  g_mixed, rownorm, partials, g_ctrl, g_scal may be NULL in stage 0.
+extern "C" int ias_voice_backward(int stage, const float* ctrl, const void* vconst, const float* noise, const float* g_mixed,
+                                  const float* rownorm, float* planes, double* tile_sums, double* partials, float* g_ctrl,
+                                  double* g_scal, int B, int T, int Tc, int sample_rate, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  if (stage < -1 || stage > 1) return IAS_ERR_ARG;
   if (!ctrl || !vconst || !planes || !tile_sums) return IAS_ERR_ARG;
   if (stage != 0 && (!noise || !g_mixed || !partials || !g_ctrl)) return IAS_ERR_ARG;
   if (B <= 0 || B > 65535 || T <= 1 || Tc <= 1 || sample_rate <= 0) return IAS_ERR_ARG;

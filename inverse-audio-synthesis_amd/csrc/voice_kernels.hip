@@ -957,10 +957,11 @@ static int voice_control_launch(const float* params01, float* ctrl, void* vconst
   return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
 }
 
-// env: scratch [B][8][Tc] floats (six envelopes + two LFO outputs), also an output for diagnostics.
-extern "C" int ias_voice_control(const float* params01, float* ctrl, void* vconst, float* env, int B, int Tc,
+// env: scratch [B][8][Tc] floats (six envelopes + two LFO outputs), also an output for diagnostics.  dbg (NULL: not
+// wanted): the control-rate intermediates [B][10][Tc] (6 envelopes, 2 LFO phases, 2 LFO outputs).
+extern "C" int ias_voice_control(const float* params01, float* ctrl, void* vconst, float* env, float* dbg, int B, int Tc,
                                  int control_rate, void* stream_) {
-  return voice_control_launch(params01, ctrl, vconst, env, nullptr, B, Tc, control_rate, stream_);
+  return voice_control_launch(params01, ctrl, vconst, env, dbg, B, Tc, control_rate, stream_);
 }
 
 // The same pass into the ctrl / vconst / env regions of an ias_voice_render workspace (the layout stays private to
@@ -975,13 +976,6 @@ extern "C" int ias_voice_control_ws(const float* params01, void* workspace, long
   char* ws = (char*)workspace;
   return voice_control_launch(params01, (float*)(ws + w.off_ctrl), ws + w.off_vconst, (float*)(ws + w.off_env), nullptr,
                               B, Tc, control_rate, stream_);
-}
-
-// Same, plus the control-rate intermediates dbg [B][10][Tc] (6 envelopes, 2 LFO phases, 2 LFO outputs).
-extern "C" int ias_voice_control_debug(const float* params01, float* ctrl, void* vconst, float* env, float* dbg,
-                                       int B, int Tc, int control_rate, void* stream_) {
-  if (!dbg) return IAS_ERR_ARG;
-  return voice_control_launch(params01, ctrl, vconst, env, dbg, B, Tc, control_rate, stream_);
 }
 
 // Persistent grid of the audio-rate kernel: resident workgroups per CU (occupancy query, cached) x CUs.
@@ -1076,8 +1070,8 @@ extern "C" int ias_voice_render(const float* params01, const float* noise, float
   const VoiceWs w = voice_ws_layout(B, T, Tc);
   if ((size_t)workspace_bytes < w.total) return IAS_ERR_WORKSPACE;
   char* ws = (char*)workspace;
-  rc = ias_voice_control(params01, (float*)(ws + w.off_ctrl), ws + w.off_vconst, (float*)(ws + w.off_env), B, Tc,
-                         control_rate, stream_);
+  rc = ias_voice_control(params01, (float*)(ws + w.off_ctrl), ws + w.off_vconst, (float*)(ws + w.off_env), nullptr, B,
+                         Tc, control_rate, stream_);
   for (int stage = 0; stage < (normalize ? 2 : 1) && rc == IAS_OK; ++stage)
     rc = ias_voice_stage(stage, math_mode, noise, audio, workspace, workspace_bytes, B, T, Tc, sample_rate, stream_);
   return rc;

@@ -7,7 +7,7 @@ Same public names and contracts: ``VICReg(cfg, backbone_audio, backbone_param)``
 imported -- here it works, over RCCL), ``exclude_bias_and_norm`` (:98-99).
 
 The loss forward is the HIP path (csrc/vicreg_kernels.hip: fp32 column statistics, bf16 MFMA Gram with
-fp32 accumulation, fused off-diagonal square-sum).  The backward is HIP as well (ias_vicreg_backward): closed form
+fp32 accumulation, fused off-diagonal square-sum).  The backward is HIP as well (ias_vicreg_backward4_ld): closed form
 with the B x B Gram identity  d cov_loss / d xc = 4/((Bc-1)^2 D) * ((xc xc^T) xc - xc diag(xc^T xc)) -- both
 products on the matrix cores, one elementwise epilogue -- so no D x D matrix is ever materialised in either direction.
 """
@@ -88,7 +88,7 @@ class _VICRegLossFn(torch.autograd.Function):
 
 class _VICRegPairLossFn(torch.autograd.Function):
     """The same loss on xy [B, 2 D] = cat(x, y, dim=1), consumed in place as two column blocks (ias_vicreg_loss_ld) and
-    differentiated into ONE [B, 2 D] cotangent (ias_vicreg_backward_ld): the shape in which the gathered batch arrives
+    differentiated into ONE [B, 2 D] cotangent (ias_vicreg_backward4_ld): the shape in which the gathered batch arrives
     from, and its gradient goes back to, the single collective of ``gather_rows``.  No split / cat copies."""
 
     @staticmethod

@@ -289,19 +289,22 @@ class Voice(nn.Module):
             raise RuntimeError("voice render: a tile's bounded wait for its predecessors expired "
                                "(ias_voice_read_status != 0); the audio of that tile is NaN")
 
-    def control_debug(self, params01=None):
-        """Control-rate intermediates [B,10,Tc] (envelopes, LFO phases, LFO outputs) for tests."""
+    def _control(self, params01, with_dbg):
+        """One control-rate pass -> (ctrl [B,5,Tc], vconst [B,16], dbg [B,10,Tc] or None)."""
         c = self.synthconfig
         p = (self.params01 if params01 is None else params01).detach().to(torch.float32).contiguous()
-        lib = _lib.load()
         ctrl = torch.empty((c.batch_size, 5, c.control_buffer_size), dtype=torch.float32, device=p.device)
         vconst = torch.empty((c.batch_size, 16), dtype=torch.float32, device=p.device)
-        dbg = torch.empty((c.batch_size, 10, c.control_buffer_size), dtype=torch.float32, device=p.device)
         env = torch.empty((c.batch_size, 8, c.control_buffer_size), dtype=torch.float32, device=p.device)
-        st = lib.ias_voice_control_debug(_lib.ptr(p), _lib.ptr(ctrl), _lib.ptr(vconst), _lib.ptr(env), _lib.ptr(dbg), c.batch_size,
-                                         c.control_buffer_size, c.control_rate, _lib.stream())
-        _lib.check(st, "ias_voice_control_debug")
-        return dbg
+        dbg = torch.empty((c.batch_size, 10, c.control_buffer_size), dtype=torch.float32, device=p.device) if with_dbg else None
+        st = _lib.load().ias_voice_control(_lib.ptr(p), _lib.ptr(ctrl), _lib.ptr(vconst), _lib.ptr(env), _lib.ptr(dbg),
+                                           c.batch_size, c.control_buffer_size, c.control_rate, _lib.stream())
+        _lib.check(st, "ias_voice_control")
+        return ctrl, vconst, dbg
+
+    def control_debug(self, params01=None):
+        """Control-rate intermediates [B,10,Tc] (envelopes, LFO phases, LFO outputs) for tests."""
+        return self._control(params01, True)[2]
 
     def rendered_control(self, workspace=None):
         """(ctrl [B,5,Tc] fp32, vconst [B,16] fp32) copied out of the workspace the last render used: the control
@@ -331,16 +334,7 @@ class Voice(nn.Module):
 
     def control_signals(self, params01=None):
         """Mod-matrix outputs [B,5,Tc] of the control-rate kernel (diagnostics / tests)."""
-        c = self.synthconfig
-        p = (self.params01 if params01 is None else params01).detach().to(torch.float32).contiguous()
-        lib = _lib.load()
-        ctrl = torch.empty((c.batch_size, 5, c.control_buffer_size), dtype=torch.float32, device=p.device)
-        vconst = torch.empty((c.batch_size, 16), dtype=torch.float32, device=p.device)
-        env = torch.empty((c.batch_size, 8, c.control_buffer_size), dtype=torch.float32, device=p.device)
-        st = lib.ias_voice_control(_lib.ptr(p), _lib.ptr(ctrl), _lib.ptr(vconst), _lib.ptr(env), c.batch_size,
-                                   c.control_buffer_size, c.control_rate, _lib.stream())
-        _lib.check(st, "ias_voice_control")
-        return ctrl, vconst
+        return self._control(params01, False)[:2]
 
     def forward(self, batch_idx=None):
         if batch_idx is not None:

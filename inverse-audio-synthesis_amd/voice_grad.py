@@ -165,8 +165,8 @@ def normalisation_rows(g_audio, audio, peaks):
 
 class BackwardPrelude:
     """The parts of the two backward calls that do not see a cotangent -- the phase increments + tile sums of the
-    audio-rate adjoint (``ias_voice_backward_sums_stage(0)``) and the envelope values of the control-rate adjoint
-    (``ias_voice_control_backward_ws_stage(0)``) -- launched at RENDER time on a stream of their own, beside whatever the
+    audio-rate adjoint (``ias_voice_backward`` stage 0) and the envelope values of the control-rate adjoint
+    (``ias_voice_control_backward_ws`` stage 0) -- launched at RENDER time on a stream of their own, beside whatever the
     caller computes between the render and its backward (the losses).  ``join()`` makes the current stream wait for them.
     ``IAS_VOICE_PRELUDE=0``: everything in the backward, as before."""
 
@@ -195,16 +195,15 @@ class BackwardPrelude:
         for t in (self.planes, self.tile_sums, self.cws, p, ctrl, vconst):
             t.record_stream(side)
         with torch.cuda.stream(side):
-            st = lib.ias_voice_backward_sums_stage(0, _lib.ptr(ctrl), _lib.ptr(vconst), None, None, None, _lib.ptr(self.planes),
-                                                   _lib.ptr(self.tile_sums), None, None, None, B, T, Tc, c.sample_rate,
-                                                   _lib.stream())
-            _lib.check(st, "ias_voice_backward_sums_stage")
-            st = lib.ias_voice_control_backward_ws_stage(0, _lib.ptr(p), None, None, None, _lib.ptr(self.cws), self.cws.numel(),
-                                                         B, Tc, c.control_rate, _lib.stream())
+            st = lib.ias_voice_backward(0, _lib.ptr(ctrl), _lib.ptr(vconst), None, None, None, _lib.ptr(self.planes),
+                                        _lib.ptr(self.tile_sums), None, None, None, B, T, Tc, c.sample_rate, _lib.stream())
+            _lib.check(st, "ias_voice_backward")
+            st = lib.ias_voice_control_backward_ws(0, _lib.ptr(p), None, None, None, _lib.ptr(self.cws), self.cws.numel(),
+                                                   B, Tc, c.control_rate, _lib.stream())
             if st == -2:                                  # control buffer too long for the HIP form: the torch graph does it all
                 self.ctrl_ok = False
             else:
-                _lib.check(st, "ias_voice_control_backward_ws_stage")
+                _lib.check(st, "ias_voice_control_backward_ws")
         self.side = side
 
     def join(self):
@@ -249,10 +248,7 @@ def audio_rate_backward(voice, params01, g_mixed, rownorm=None, control=None, pr
     g_scal = torch.empty((B, lib.ias_voice_grad_nscalars()), dtype=torch.float64, device=dev)
     args = (_lib.ptr(ctrl), _lib.ptr(vconst), _lib.ptr(voice.noise), _lib.ptr(g_mixed), _lib.ptr(rownorm), _lib.ptr(planes),
             _lib.ptr(tile_sums), _lib.ptr(partials), _lib.ptr(g_ctrl), _lib.ptr(g_scal), B, T, Tc, c.sample_rate, _lib.stream())
-    if prelude is not None:
-        _lib.check(lib.ias_voice_backward_sums_stage(1, *args), "ias_voice_backward_sums_stage")
-    else:
-        _lib.check(lib.ias_voice_backward_sums(*args), "ias_voice_backward_sums")
+    _lib.check(lib.ias_voice_backward(1 if prelude is not None else -1, *args), "ias_voice_backward")
     return g_ctrl, g_scal
 
 
@@ -302,15 +298,11 @@ def _control_backward_hip(cfg, p, g_ctrl, g_scal, prelude=None):
     g_scal = g_scal.to(torch.float64).contiguous()
     out = torch.empty((p.shape[0], S.NPARAMS), dtype=torch.float32, device=p.device)
     if prelude is not None and prelude.ctrl_ok:
-        ws = prelude.cws                                  # stage 0 (the envelope values) ran beside the losses
-        st = lib.ias_voice_control_backward_ws_stage(1, _lib.ptr(p), _lib.ptr(g_ctrl), _lib.ptr(g_scal), _lib.ptr(out),
-                                                     _lib.ptr(ws), ws.numel(), p.shape[0], cfg.control_buffer_size,
-                                                     cfg.control_rate, _lib.stream())
-        _lib.check(st, "ias_voice_control_backward_ws_stage")
-        return out
-    nws = lib.ias_voice_control_backward_ws_bytes(p.shape[0], cfg.control_buffer_size)
-    ws = torch.empty(max(int(nws), 16), dtype=torch.uint8, device=p.device)
-    st = lib.ias_voice_control_backward_ws(_lib.ptr(p), _lib.ptr(g_ctrl), _lib.ptr(g_scal), _lib.ptr(out), _lib.ptr(ws),
+        stage, ws = 1, prelude.cws                        # stage 0 (the envelope values) ran beside the losses
+    else:
+        nws = lib.ias_voice_control_backward_ws_bytes(p.shape[0], cfg.control_buffer_size)
+        stage, ws = -1, torch.empty(max(int(nws), 16), dtype=torch.uint8, device=p.device)
+    st = lib.ias_voice_control_backward_ws(stage, _lib.ptr(p), _lib.ptr(g_ctrl), _lib.ptr(g_scal), _lib.ptr(out), _lib.ptr(ws),
                                            ws.numel(), p.shape[0], cfg.control_buffer_size, cfg.control_rate, _lib.stream())
     if st == -2:      # IAS_ERR_UNSUPPORTED: control buffer too long for LDS -> torch graph
         return None

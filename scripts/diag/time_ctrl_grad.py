@@ -15,7 +15,7 @@ SPLIT = os.environ.get("SPLIT", "1") != "0"
 ws = torch.empty(int(lib.ias_voice_control_backward_ws_bytes(B, Tc)), dtype=torch.uint8, device=dev)
 def run():
     if SPLIT:
-        st = lib.ias_voice_control_backward_ws(_lib.ptr(p), _lib.ptr(g_ctrl), _lib.ptr(g_scal), _lib.ptr(out), _lib.ptr(ws), ws.numel(), B, Tc, 441, _lib.stream())
+        st = lib.ias_voice_control_backward_ws(-1, _lib.ptr(p), _lib.ptr(g_ctrl), _lib.ptr(g_scal), _lib.ptr(out), _lib.ptr(ws), ws.numel(), B, Tc, 441, _lib.stream())
     else:
         st = lib.ias_voice_control_backward(_lib.ptr(p), _lib.ptr(g_ctrl), _lib.ptr(g_scal), _lib.ptr(out), B, Tc, 441, _lib.stream())
     assert st == 0, st

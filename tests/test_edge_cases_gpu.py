@@ -129,10 +129,10 @@ def test_c_abi_rejects_bad_arguments(lib, dev):
     zd = torch.zeros(64, device=dev, dtype=torch.float64)
     p = _lib.ptr
     ARG, UNSUP = -1, -2
-    assert lib.ias_voice_backward(None, p(z), p(z), p(z), p(z), p(zd), p(zd), p(z), 1, 16000, 441, 16000, None) == ARG
-    assert lib.ias_voice_backward(p(z), p(z), p(z), p(z), p(z), p(zd), p(zd), p(z), 0, 16000, 441, 16000, None) == ARG
+    assert lib.ias_voice_backward(-1, None, p(z), p(z), p(z), None, p(z), p(zd), p(zd), p(z), None, 1, 16000, 441, 16000, None) == ARG
+    assert lib.ias_voice_backward(-1, p(z), p(z), p(z), p(z), None, p(z), p(zd), p(zd), p(z), None, 0, 16000, 441, 16000, None) == ARG
     # a control rate too close to the sample rate: the transposed upsample cannot stage its intervals
-    assert lib.ias_voice_backward(p(z), p(z), p(z), p(z), p(z), p(zd), p(zd), p(z), 1, 64, 60, 16000, None) == UNSUP
+    assert lib.ias_voice_backward(-1, p(z), p(z), p(z), p(z), None, p(z), p(zd), p(zd), p(z), None, 1, 64, 60, 16000, None) == UNSUP
     assert lib.ias_voice_control_backward(None, p(z), p(zd), p(z), 1, 441, 441, None) == ARG
     assert lib.ias_voice_control_backward(p(z), p(z), p(zd), p(z), 1, 441, 440, None) == UNSUP     # kernel is built for 441
     assert lib.ias_voice_control_backward(p(z), p(z), p(zd), p(z), 1, 100000, 441, None) == UNSUP  # does not fit LDS

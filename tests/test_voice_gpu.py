@@ -275,8 +275,8 @@ def test_control_pass_without_library_math_equals_the_library_forms(lib, dev, mo
         vconst = torch.empty((B, 16), device=dev)
         env = torch.empty((B, 8, c.control_buffer_size), device=dev)
         dbg = torch.empty((B, 10, c.control_buffer_size), device=dev)
-        _lib.check(l.ias_voice_control_debug(_lib.ptr(v.params01), _lib.ptr(ctrl), _lib.ptr(vconst), _lib.ptr(env), _lib.ptr(dbg), B,
-                                             c.control_buffer_size, c.control_rate, _lib.stream()), "ias_voice_control_debug")
+        _lib.check(l.ias_voice_control(_lib.ptr(v.params01), _lib.ptr(ctrl), _lib.ptr(vconst), _lib.ptr(env), _lib.ptr(dbg), B,
+                                       c.control_buffer_size, c.control_rate, _lib.stream()), "ias_voice_control")
         torch.cuda.synchronize()
         return ctrl.cpu(), vconst.cpu(), env.cpu(), dbg.cpu()
 

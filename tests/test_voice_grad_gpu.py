@@ -238,12 +238,12 @@ def test_control_backward_in_four_launches_equals_the_single_kernel(lib, dev):
     _lib.check(lib.ias_voice_control_backward(_lib.ptr(p), _lib.ptr(g_ctrl), _lib.ptr(g_scal), _lib.ptr(one), B, Tc, 441,
                                               _lib.stream()), "ias_voice_control_backward")
     ws = torch.empty(int(lib.ias_voice_control_backward_ws_bytes(B, Tc)), dtype=torch.uint8, device=dev)
-    _lib.check(lib.ias_voice_control_backward_ws(_lib.ptr(p), _lib.ptr(g_ctrl), _lib.ptr(g_scal), _lib.ptr(four), _lib.ptr(ws),
+    _lib.check(lib.ias_voice_control_backward_ws(-1, _lib.ptr(p), _lib.ptr(g_ctrl), _lib.ptr(g_scal), _lib.ptr(four), _lib.ptr(ws),
                                                  ws.numel(), B, Tc, 441, _lib.stream()), "ias_voice_control_backward_ws")
     assert torch.isfinite(one[2:]).all()                 # rows 0/1 sit on the range ends, where the curve maps' derivatives
     assert torch.allclose(one, four, rtol=0.0, atol=0.0, equal_nan=True)      # are not finite (in torch autograd neither)
     small = torch.empty(16, dtype=torch.uint8, device=dev)
-    assert lib.ias_voice_control_backward_ws(_lib.ptr(p), _lib.ptr(g_ctrl), _lib.ptr(g_scal), _lib.ptr(four), _lib.ptr(small),
+    assert lib.ias_voice_control_backward_ws(-1, _lib.ptr(p), _lib.ptr(g_ctrl), _lib.ptr(g_scal), _lib.ptr(four), _lib.ptr(small),
                                              small.numel(), B, Tc, 441, _lib.stream()) == -4      # IAS_ERR_WORKSPACE
 
 
