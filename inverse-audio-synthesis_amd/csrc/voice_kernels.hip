@@ -327,7 +327,7 @@ static size_t voice_control_fused_lds(int Tc) {
 #endif
 
 // -------------------------------------------------------------------- audio rate
-#define VOICE_MAXCTRL 320  // control points staged per tile (covers sample rates down to ~6 kHz)
+#define VOICE_MAXCTRL 320  // control points one tile may span (covers sample rates down to ~6 kHz)
 #define VOICE_SPIN_LIMIT (1u << 24)
 #ifndef VOICE_SPIN_SLEEP
 #define VOICE_SPIN_SLEEP 8   // s_sleep units (64 clocks) between two polls of the look-back (2: 98-100 us, 8: 96-97.5, 32: 96-99; same box)
@@ -358,7 +358,7 @@ __device__ unsigned long long* g_voice_stamps = nullptr;
 extern "C" int ias_voice_debug_set_stamps(unsigned long long* p) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_voice_stamps), &p, sizeof(p)) == hipSuccess ? 0 : -3;
 }
-#define VSTAMP(slot) do { if (g_voice_stamps && have_cur && lane == 0) { unsigned long long* sp_ = g_voice_stamps + ((size_t)(cur.b * ntiles + cur.tile) * 4 + wave) * 12; sp_[slot] = __builtin_amdgcn_s_memtime(); if ((slot) == 0) sp_[10] = __builtin_amdgcn_s_memrealtime(); if ((slot) == 6) sp_[11] = __builtin_amdgcn_s_memrealtime(); } } while (0)
+#define VSTAMP(slot) do { if (g_voice_stamps && have_cur && lane == 0) { unsigned long long* sp_ = g_voice_stamps + ((size_t)(cur.b * ntiles + cur.tile) * 4 + wave) * 12; sp_[slot] = __builtin_amdgcn_s_memtime(); if ((slot) == 0) sp_[10] = __builtin_amdgcn_s_memrealtime(); if ((slot) == 5) sp_[11] = __builtin_amdgcn_s_memrealtime(); } } while (0)
 #else
 #define VSTAMP(slot) do {} while (0)
 #endif
@@ -447,36 +447,32 @@ __device__ __forceinline__ int voice_take_ticket(unsigned int* counters, int& c,
   }
   return -1;
 }
-// One tile = 4096 consecutive samples of one voice; all fields are workgroup-uniform.
+// One tile = 4096 consecutive samples of one voice.  tile, b, j_tile and fast are workgroup-uniform; c_lo and ncp are the
+// WAVE's own: the control rows its 1024 samples read.  Row k serves the samples with trunc(scale j) == k and holds
+// both ends of their lerp, (c[k], c[min(k + 1, Tc - 1)]), so the rows of a wave are those of its first to its last sample
+// (11 or 12 at the headline shape: at most 64 / IAS_NCTRL, one (signal, row) pair per lane).
 struct VoiceTile {
   int tile, b, j_tile, c_lo, ncp;
   bool fast;   // a full tile of a row whose length is a multiple of 4 samples (LDS-DMA / whole-KB path)
 };
-__device__ __forceinline__ VoiceTile voice_tile_of(int ticket, int nvoices, int T, int Tc, float scale) {
+#define VOICE_WAVE_SAMPLES (64 * VOICE_SPT)
+__device__ __forceinline__ VoiceTile voice_tile_of(int ticket, int nvoices, int T, int Tc, float scale, int wave_u) {
   VoiceTile t;
   const int c = ticket >> 24, n = ticket & 0xffffff;
   const int nv_c = (nvoices - c + VOICE_NCOUNTERS - 1) / VOICE_NCOUNTERS;
   t.tile = n / nv_c;
   t.b = (n - t.tile * nv_c) * VOICE_NCOUNTERS + c;
   t.j_tile = t.tile * VOICE_TILE;
-  const int j_last = min(t.j_tile + VOICE_TILE, T) - 1;
+  // (a wave beyond the end of a ragged last tile stages the row's last point; what its lanes compute is discarded)
+  const int j_first = min(t.j_tile + wave_u * VOICE_WAVE_SAMPLES, T - 1);
+  const int j_last = min(t.j_tile + (wave_u + 1) * VOICE_WAVE_SAMPLES, T) - 1;
   int i0, i1; float w0, w1;
-  ias_interp_pos(t.j_tile, scale, Tc, i0, i1, w0, w1);
+  ias_interp_pos(j_first, scale, Tc, i0, i1, w0, w1);
   t.c_lo = i0;
   ias_interp_pos(j_last, scale, Tc, i0, i1, w0, w1);
-  t.ncp = i1 - t.c_lo + 1;                       // host guarantees ncp <= maxctrl
+  t.ncp = i0 - t.c_lo + 1;                       // host guarantees ncp <= wave_maxctrl
   t.fast = (t.j_tile + VOICE_TILE <= T) && (T & 3) == 0;
   return t;
-}
-// The control points a tile interpolates between -> LDS rows [ncp][IAS_NCTRL] of (c[i], c[min(i + 1, Tc - 1)]) pairs:
-// one ds_read_b64 at an immediate offset from the point's address fetches both ends of a lerp.
-__device__ __forceinline__ void voice_stage_ctrl(char* dst, const float* __restrict__ ctrl, const VoiceTile& t, int Tc) {
-  const float* cb = ctrl + (size_t)t.b * IAS_NCTRL * Tc;
-  for (int i = threadIdx.x; i < IAS_NCTRL * t.ncp; i += AUDIO_THREADS) {
-    const int k = i / t.ncp, c = i - k * t.ncp;
-    const float* crow = cb + k * Tc;
-    reinterpret_cast<float2*>(dst)[c * IAS_NCTRL + k] = make_float2(crow[t.c_lo + c], crow[min(t.c_lo + c + 1, Tc - 1)]);
-  }
 }
 
 // ---- phase A of a tile: the lane's 2 x 16 phase increments (registers), their fp64 totals, the wave scan of the
@@ -602,7 +598,7 @@ __device__ __forceinline__ void voice_phase_b(const char* s_ctrl, float* s_stage
   }
 }
 
-// element i (< IAS_NCTRL * ncp) of a tile's control stage: signal k = i / ncp, point c = i % ncp
+// element i (< IAS_NCTRL * ncp) of a wave's control stage: signal k = i / ncp, point c = i % ncp
 __device__ __forceinline__ float2 voice_ctrl_elem(const float* __restrict__ ctrl, const VoiceTile& t, int Tc, int i) {
   const int k = i / t.ncp, c = i - k * t.ncp;
   const float* crow = ctrl + ((size_t)t.b * IAS_NCTRL + k) * Tc;
@@ -642,60 +638,84 @@ __device__ __forceinline__ void voice_ctrl_put(char* dst, const VoiceTile& t, in
 //   wait    -> one wave polls the predecessors' words with relaxed agent-scope loads (L1 bypass), bounded spins, and
 //              adds them up: the tile's carry-in.  An expired wait turns the carry (hence the tile's audio) into NaN.
 //   roles   -> wave 0 takes tickets, wave 3 looks back, wave 2 publishes: no wave carries all the serial work.
+//   sync    -> ONE workgroup barrier per tile.  Everything a wave shares with nobody needs none: its control rows (two
+//              stages per wave, filled by the wave itself from the points it fetched during the previous phase B) and its
+//              noise / audio block -- LDS operations of one wave execute in order.  What does cross waves -- wave sums,
+//              carry, ticket, wave peaks -- is buffered by iteration parity (the wave sums three deep) so that the one
+//              barrier orders every write against the reads of the iteration before: the argument is at the barrier.
+//   loop x2 -> the tile loop is unrolled by two with the two sets of increment registers swapping roles, so "next"
+//              becomes "current" by name and not by 32 register moves per lane and tile.
 // The pitch exp2 reads a 2^(i/256) table (fp64, 21.7 KB) that each workgroup copies to LDS once.
 #define VOICE_WAVE_LOOKBACK (AUDIO_WAVES - 1)
 #define VOICE_WAVE_PUBLISH (AUDIO_WAVES - 2)
+template <int V> struct VoiceSlot { static constexpr int value = V; };
 template <int MATH, bool FMA_DIV>
 __global__ __launch_bounds__(AUDIO_THREADS, VOICE_MIN_WAVES) __attribute__((amdgpu_num_vgpr(76))) void voice_audio_kernel(
     const float* __restrict__ ctrl, const IasVoiceConst* __restrict__ vconst,
     const float* __restrict__ noise, float* __restrict__ audio, unsigned long long* agg /* [B][ntiles][2] */,
     unsigned int* ticket_status /* VOICE_NCOUNTERS ticket counters (32 words apart), then the spin-timeout flag */,
     unsigned* __restrict__ rowpeak, int T, int Tc, int ntiles, int nvoices, double inv_sample_rate, float sr_f,
-    float sr_r, float scale, int maxctrl) {
-  // dynamic LDS: exp2 table | per-wave noise / audio blocks [AUDIO_WAVES][1024] floats | two control stages
+    float sr_r, float scale, int wave_maxctrl) {
+  // dynamic LDS: exp2 table | per-wave noise / audio blocks [AUDIO_WAVES][1024] floats | control stages [AUDIO_WAVES][2]
   extern __shared__ __attribute__((aligned(16))) double dyn_smem_d[];
   double* s_tab = dyn_smem_d;
   float* s_stage = reinterpret_cast<float*>(dyn_smem_d + VOICE_TAB_DOUBLES);
-  char* s_ctrl0 = reinterpret_cast<char*>(s_stage + VOICE_TILE);
-  const int ctrl_bytes = maxctrl * VOICE_CTRL_ROW;
-  __shared__ double s_wsum[2][2][AUDIO_WAVES];   // [slot][vco][wave]
-  __shared__ double s_carry[2];
-  __shared__ float s_max[AUDIO_WAVES];
-  __shared__ int s_ticket;
+  const int ctrl_bytes = wave_maxctrl * VOICE_CTRL_ROW;
+  __shared__ double s_wsum[3][2][AUDIO_WAVES];   // [tile % 3][vco][wave]
+  __shared__ double s_carry[2][2];               // [slot][vco]
+  __shared__ float s_max[2][AUDIO_WAVES];        // [slot][wave]
+  __shared__ int s_ticket[2];                    // [slot]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  char* s_ctrl_w = reinterpret_cast<char*>(s_stage + VOICE_TILE) + wave_u * 2 * ctrl_bytes;   // this wave's two stages
   int my_counter = blockIdx.x % VOICE_NCOUNTERS, counters_tried = 0;   // used by thread 0 only
-  if (tid == 0) s_ticket = voice_take_ticket(ticket_status, my_counter, counters_tried, ntiles, nvoices);
+  // (slot 1: the first iteration writes slot 0 before its barrier, which not every wave has read this one by then)
+  if (tid == 0) s_ticket[1] = voice_take_ticket(ticket_status, my_counter, counters_tried, ntiles, nvoices);
   if (MATH == VOICE_MATH_CR)
     for (int i = tid; i < IAS_EXP2_TAB_LEN; i += AUDIO_THREADS) s_tab[i] = g_exp2_tab[i];
   __syncthreads();
 
   VoiceTile cur = {}, next = {};
-  bool have_cur = false;
+  bool have_cur = false, have_prev = false;
+  int prev_b = 0, prev_slot = 0;                // the tile before the current one: its row peak is still to be merged
   // the first tile: ticket and control points fetched here, synchronously
-  bool have_next = __builtin_amdgcn_readfirstlane(s_ticket) >= 0;
-  float2 pre = make_float2(0.f, 0.f);           // this thread's element of the control stage of `next`
+  bool have_next = __builtin_amdgcn_readfirstlane(s_ticket[1]) >= 0;
+  float2 pre = make_float2(0.f, 0.f);           // this lane's element of the wave's control stage of `next`
   if (have_next) {
-    next = voice_tile_of(__builtin_amdgcn_readfirstlane(s_ticket), nvoices, T, Tc, scale);
-    if (tid < IAS_NCTRL * next.ncp) pre = voice_ctrl_elem(ctrl, next, Tc, tid);
+    next = voice_tile_of(__builtin_amdgcn_readfirstlane(s_ticket[1]), nvoices, T, Tc, scale, wave_u);
+    if (lane < IAS_NCTRL * next.ncp) pre = voice_ctrl_elem(ctrl, next, Tc, lane);
   }
-  int slot = 0;                                 // s_wsum / control stage of the CURRENT tile
-  float incC1[VOICE_SPT], incC2[VOICE_SPT];     // the current tile's increments (phase B), the next tile's (phase A)
-  float incN1[VOICE_SPT], incN2[VOICE_SPT];
-  double exC1 = 0.0, exC2 = 0.0, exN1 = 0.0, exN2 = 0.0;
+  int q_cur = 2, q_next = 0;                    // s_wsum buffers of the current and the next tile
+  // two sets of increments and lane prefixes: one holds the current tile's (phase B), the other receives the next
+  // tile's (phase A); they swap roles from one half of the unrolled loop to the other
+  float incA1[VOICE_SPT], incA2[VOICE_SPT], incB1[VOICE_SPT], incB2[VOICE_SPT];
+  double exA1 = 0.0, exA2 = 0.0, exB1 = 0.0, exB2 = 0.0;
 #pragma unroll
-  for (int e = 0; e < VOICE_SPT; ++e) { incC1[e] = incC2[e] = 0.0f; }
+  for (int e = 0; e < VOICE_SPT; ++e) { incA1[e] = incA2[e] = 0.0f; }
 
-  while (have_cur || have_next) {
+  auto merge_peak = [&](int b, int sl) {        // thread 0, behind a barrier that follows the tile's phase B
+    float m = s_max[sl][0];
+    for (int w = 1; w < AUDIO_WAVES; ++w) m = fmaxf(m, s_max[sl][w]);
+    atomicMax(rowpeak + b, __float_as_uint(m));  // m >= 0: uint order == float order
+  };
+
+  // one iteration: slot = its parity (control stage, carry, wave peaks, ticket of the CURRENT tile: slot; of the next:
+  // slot ^ 1); incC / exC belong to the current tile, incN / exN receive the next tile's
+  auto iteration = [&](auto slot_c, const float (&incC1)[VOICE_SPT], const float (&incC2)[VOICE_SPT], double exC1, double exC2,
+                       float (&incN1)[VOICE_SPT], float (&incN2)[VOICE_SPT], double& exN1, double& exN2)
+                       __attribute__((always_inline)) {
+    constexpr int slot = decltype(slot_c)::value;
     gu64* row = (gu64*)(agg + ((size_t)cur.b * ntiles) * 2);
     VSTAMP(0);
     // (the put comes first: its wait for the control points' loads would otherwise cover the requests issued below)
     if (have_next) {
-      // the next tile's control points (fetched during the previous phase B) -> LDS
-      char* dst = s_ctrl0 + (slot ^ 1) * ctrl_bytes;
+      // the wave's control rows of the next tile (fetched during the previous phase B) -> its own stage.  The stage was
+      // last read by this wave's phase B of the previous iteration: same wave, program order, no barrier.
+      char* dst = s_ctrl_w + (slot ^ 1) * ctrl_bytes;
       const IasVoiceConst vcp = vconst[next.b];
-      if (tid < IAS_NCTRL * next.ncp) voice_ctrl_put(dst, next, tid, pre, vcp);
-      for (int i = tid + AUDIO_THREADS; i < IAS_NCTRL * next.ncp; i += AUDIO_THREADS)   // windows wider than 51 points
+      if (lane < IAS_NCTRL * next.ncp) voice_ctrl_put(dst, next, lane, pre, vcp);
+      for (int i = lane + 64; i < IAS_NCTRL * next.ncp; i += 64)   // a wave that reads more than 12 rows
         voice_ctrl_put(dst, next, i, voice_ctrl_elem(ctrl, next, Tc, i), vcp);
     }
     unsigned long long early1 = VOICE_READY_BIT, early2 = VOICE_READY_BIT;
@@ -706,15 +726,13 @@ __global__ __launch_bounds__(AUDIO_THREADS, VOICE_MIN_WAVES) __attribute__((amdg
         early2 = __hip_atomic_load(row + lane * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       if (cur.fast) {
-        const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-        const float* nsrc = noise + (size_t)cur.b * T + cur.j_tile + wave_u * (64 * VOICE_SPT) + 4 * (lane ^ (lane >> 4));
+        const float* nsrc = noise + (size_t)cur.b * T + cur.j_tile + wave_u * VOICE_WAVE_SAMPLES + 4 * (lane ^ (lane >> 4));
 #pragma unroll
         for (int q = 0; q < VOICE_SPT / 4; ++q)
           __builtin_amdgcn_global_load_lds((voice_glb_void*)(nsrc + q * 256),
-                                           (voice_lds_void*)(s_stage + wave_u * (64 * VOICE_SPT) + q * 256), 16, 0, 0);
+                                           (voice_lds_void*)(s_stage + wave_u * VOICE_WAVE_SAMPLES + q * 256), 16, 0, 0);
       }
     }
-    __syncthreads();   // (1) the next tile's control points are staged
     VSTAMP(1);
     unsigned after_raw = 0;
     int after_c = 0;
@@ -730,12 +748,12 @@ __global__ __launch_bounds__(AUDIO_THREADS, VOICE_MIN_WAVES) __attribute__((amdg
 #else
       if (next.fast)
 #endif
-        voice_phase_a<MATH, FMA_DIV, true>(s_ctrl0 + (slot ^ 1) * ctrl_bytes, s_tab, vcn, next, T, inv_sample_rate, sr_f, sr_r,
-                                           scale, incN1, incN2, exN1, exN2, s_wsum[slot ^ 1]);
+        voice_phase_a<MATH, FMA_DIV, true>(s_ctrl_w + (slot ^ 1) * ctrl_bytes, s_tab, vcn, next, T, inv_sample_rate, sr_f, sr_r,
+                                           scale, incN1, incN2, exN1, exN2, s_wsum[q_next]);
 #ifndef VOICE_ANALYZE_FULL_ONLY
       else
-        voice_phase_a<MATH, FMA_DIV, false>(s_ctrl0 + (slot ^ 1) * ctrl_bytes, s_tab, vcn, next, T, inv_sample_rate, sr_f, sr_r,
-                                            scale, incN1, incN2, exN1, exN2, s_wsum[slot ^ 1]);
+        voice_phase_a<MATH, FMA_DIV, false>(s_ctrl_w + (slot ^ 1) * ctrl_bytes, s_tab, vcn, next, T, inv_sample_rate, sr_f, sr_r,
+                                            scale, incN1, incN2, exN1, exN2, s_wsum[q_next]);
 #endif
       if (tid == 0) {
         const int nv_c = (nvoices - after_c + VOICE_NCOUNTERS - 1) / VOICE_NCOUNTERS;
@@ -745,10 +763,10 @@ __global__ __launch_bounds__(AUDIO_THREADS, VOICE_MIN_WAVES) __attribute__((amdg
           ++counters_tried;
           tk = voice_take_ticket(ticket_status, my_counter, counters_tried, ntiles, nvoices);
         }
-        s_ticket = tk;
+        s_ticket[slot] = tk;
       }
     } else if (tid == 0) {
-      s_ticket = -1;
+      s_ticket[slot] = -1;
     }
     VSTAMP(2);
     // ---- the current tile's carry-in: its predecessors' sums
@@ -785,27 +803,39 @@ __global__ __launch_bounds__(AUDIO_THREADS, VOICE_MIN_WAVES) __attribute__((amdg
           __hip_atomic_store((gu32*)ticket_status + VOICE_NCOUNTERS * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           __hip_atomic_store((gu32*)ticket_status - 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sticky (VoiceWs::off_sticky)
         }
-        s_carry[0] = a1; s_carry[1] = a2;
+        s_carry[slot][0] = a1; s_carry[slot][1] = a2;
       }
     }
     VSTAMP(3);
-    __syncthreads();   // (2) the next tile's wave sums, the current tile's carry, the noise blocks, the ticket after next
+    // The one barrier of the tile: the next tile's wave sums, the current tile's carry, the noise blocks, the ticket after
+    // next.  It is also all that separates the iterations.  Call this iteration i and its barrier B(i):
+    //   s_ticket[slot], s_carry[slot]  written before B(i), read after B(i) and before B(i + 1); written again before
+    //                                  B(i + 2): B(i + 1) lies between (the initial ticket sits in slot 1 for this reason).
+    //   s_wsum[q_next]                 written before B(i), read after B(i) (publish) and after B(i + 1) (phase B); that
+    //                                  buffer's turn comes again in iteration i + 3, before B(i + 3): B(i + 2) lies between.
+    //                                  (Two buffers would not do: the write before B(i + 2) could pass a slow wave's read
+    //                                  behind B(i + 1).)
+    //   s_max[slot]                    written after B(i) (end of phase B), read by thread 0 after B(i + 1) (or after the
+    //                                  barrier behind the loop), written again after B(i + 2).
+    //   control stages, noise blocks   wave-private.
+    __syncthreads();
     VSTAMP(4);
+    if (have_prev && tid == 0) merge_peak(prev_b, slot ^ 1);   // the previous tile's row peak
     if (have_next && wave == VOICE_WAVE_PUBLISH && lane < 2) {
       // publish the next tile's sums: from here on nobody waits for this workgroup on its account
       double a = 0.0;
-      for (int w = 0; w < AUDIO_WAVES; ++w) a += s_wsum[slot ^ 1][lane][w];
+      for (int w = 0; w < AUDIO_WAVES; ++w) a += s_wsum[q_next][lane][w];
       gu64* nrow_agg = (gu64*)(agg + ((size_t)next.b * ntiles) * 2);
       __hip_atomic_store(nrow_agg + next.tile * 2 + lane, (unsigned long long)__double_as_longlong(a) | VOICE_READY_BIT,
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    // the tile after next: its control points are requested now and land during phase B
-    const int t_after = __builtin_amdgcn_readfirstlane(s_ticket);
+    // the tile after next: the wave's control points are requested now and land during phase B
+    const int t_after = __builtin_amdgcn_readfirstlane(s_ticket[slot]);
     const bool have_after = t_after >= 0;
     VoiceTile after = {};
     if (have_after) {
-      after = voice_tile_of(t_after, nvoices, T, Tc, scale);
-      if (tid < IAS_NCTRL * after.ncp) pre = voice_ctrl_elem(ctrl, after, Tc, tid);
+      after = voice_tile_of(t_after, nvoices, T, Tc, scale, wave_u);
+      if (lane < IAS_NCTRL * after.ncp) pre = voice_ctrl_elem(ctrl, after, Tc, lane);
     }
     if (have_cur) {
       const IasVoiceConst vc = vconst[cur.b];
@@ -815,34 +845,36 @@ __global__ __launch_bounds__(AUDIO_THREADS, VOICE_MIN_WAVES) __attribute__((amdg
 #else
       if (cur.fast)
 #endif
-        voice_phase_b<true>(s_ctrl0 + slot * ctrl_bytes, s_stage, vc, cur, noise + (size_t)cur.b * T, audio + (size_t)cur.b * T,
-                            T, scale, incC1, incC2, exC1, exC2, s_carry, s_wsum[slot], pk);
+        voice_phase_b<true>(s_ctrl_w + slot * ctrl_bytes, s_stage, vc, cur, noise + (size_t)cur.b * T, audio + (size_t)cur.b * T,
+                            T, scale, incC1, incC2, exC1, exC2, s_carry[slot], s_wsum[q_cur], pk);
 #ifndef VOICE_ANALYZE_FULL_ONLY
       else
-        voice_phase_b<false>(s_ctrl0 + slot * ctrl_bytes, s_stage, vc, cur, noise + (size_t)cur.b * T, audio + (size_t)cur.b * T,
-                             T, scale, incC1, incC2, exC1, exC2, s_carry, s_wsum[slot], pk);
+        voice_phase_b<false>(s_ctrl_w + slot * ctrl_bytes, s_stage, vc, cur, noise + (size_t)cur.b * T, audio + (size_t)cur.b * T,
+                             T, scale, incC1, incC2, exC1, exC2, s_carry[slot], s_wsum[q_cur], pk);
 #endif
       pk = wave_max(pk);
-      if (lane == 0) s_max[wave] = pk;
+      if (lane == 0) s_max[slot][wave] = pk;
     }
     VSTAMP(5);
-    __syncthreads();   // (3) the current tile is done with its control stage, wave sums and carry; s_max is set
-    VSTAMP(6);
-    if (have_cur && tid == 0) {
-      float m = s_max[0];
-      for (int w = 1; w < AUDIO_WAVES; ++w) m = fmaxf(m, s_max[w]);
-      atomicMax(rowpeak + cur.b, __float_as_uint(m));  // m >= 0: uint order == float order
-    }
-    // rotate: next -> current, after -> next
+    // rotate: current -> previous, next -> current, after -> next (the increments rotate by the caller's argument order)
+    prev_b = cur.b;
+    have_prev = have_cur;
+    prev_slot = slot;
     cur = next;
     have_cur = have_next;
     next = after;
     have_next = have_after;
-    slot ^= 1;
-#pragma unroll
-    for (int e = 0; e < VOICE_SPT; ++e) { incC1[e] = incN1[e]; incC2[e] = incN2[e]; }
-    exC1 = exN1; exC2 = exN2;
+    q_cur = q_next;
+    q_next = q_next == 2 ? 0 : q_next + 1;
+  };
+
+  while (have_cur || have_next) {
+    iteration(VoiceSlot<0>(), incA1, incA2, exA1, exA2, incB1, incB2, exB1, exB2);
+    if (!(have_cur || have_next)) break;
+    iteration(VoiceSlot<1>(), incB1, incB2, exB1, exB2, incA1, incA2, exA1, exA2);
   }
+  __syncthreads();   // the last tile's wave peaks
+  if (have_prev && tid == 0) merge_peak(prev_b, prev_slot);
 }
 
 __global__ __launch_bounds__(256) void voice_normalize_kernel(float* __restrict__ audio,
@@ -901,14 +933,15 @@ extern "C" long long ias_voice_workspace_bytes(int B, int T, int Tc) {
   return (long long)voice_ws_layout(B, T, Tc).total;
 }
 
-// control points one tile can touch (+ the pair look-ahead and rounding slack)
-static int voice_maxctrl(int T, int Tc) {
-  return (int)((double)VOICE_TILE * (double)(Tc - 1) / (double)(T - 1)) + 6;
+// control rows one WAVE's 1024 samples can read: trunc(scale j) over 1023 steps takes at most trunc(1023 scale) + 2 values
+// (+ 2 rows of slack for the rounding of scale and of the products)
+static int voice_wave_maxctrl(int T, int Tc) {
+  return (int)((double)(VOICE_TILE / AUDIO_WAVES - 1) * (double)(Tc - 1) / (double)(T - 1)) + 4;
 }
 
 static int voice_check_dims(int B, int T, int Tc) {
   if (B <= 0 || T <= 1 || Tc <= 1 || B > 65535) return IAS_ERR_ARG;
-  // control points touched by one tile must fit the LDS stage
+  // control points touched by one tile: bounds the waves' LDS stages (a quarter of the span + 4 rows, two per wave)
   const double span = (double)VOICE_TILE * (double)(Tc - 1) / (double)(T - 1);
   if (span + 6.0 > (double)VOICE_MAXCTRL) return IAS_ERR_UNSUPPORTED;   // keeps the LDS image under ~35 KB
   return IAS_OK;
@@ -1005,8 +1038,10 @@ static void voice_audio_launch(hipStream_t stream, const VoiceWs& w, char* ws, c
                                int T, int Tc, int sample_rate) {
   const float scale = (float)(Tc - 1) / (float)(T - 1);
   const float sr_f = (float)sample_rate;
-  const int maxctrl = voice_maxctrl(T, Tc);
-  const size_t lds = sizeof(double) * VOICE_TAB_DOUBLES + sizeof(float) * VOICE_TILE + 2 * sizeof(float2) * IAS_NCTRL * (size_t)maxctrl;
+  const int wave_maxctrl = voice_wave_maxctrl(T, Tc);
+  // exp2 table | noise / audio blocks | two control stages per wave (headline shape: 21.7 + 16 + 4.4 KB, three workgroups per CU)
+  const size_t lds = sizeof(double) * VOICE_TAB_DOUBLES + sizeof(float) * VOICE_TILE +
+                     AUDIO_WAVES * 2 * sizeof(float2) * IAS_NCTRL * (size_t)wave_maxctrl;
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute((const void*)voice_audio_kernel<MATH, FMA_DIV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int ntiles = w.ntiles;
@@ -1015,7 +1050,7 @@ static void voice_audio_launch(hipStream_t stream, const VoiceWs& w, char* ws, c
                      (const float*)(ws + w.off_ctrl), (const IasVoiceConst*)(ws + w.off_vconst), noise, audio,
                      (unsigned long long*)(ws + w.off_agg), (unsigned int*)(ws + w.off_sync),
                      (unsigned*)(ws + w.off_peak), T, Tc, ntiles, B, 1.0 / (double)sample_rate, sr_f,
-                     1.0f / sr_f, scale, maxctrl);
+                     1.0f / sr_f, scale, wave_maxctrl);
 }
 
 // One stage of the render on an already-filled workspace (ias_voice_control_ws must have run into it):

@@ -26,7 +26,8 @@ assert lib.ias_voice_debug_set_stamps(ctypes.c_void_p(stamps.data_ptr())) == 0
 voice.render_audio(ws, out=audio, normalize=False)
 torch.cuda.synchronize()
 st = stamps.cpu().double()[:, 1: ntiles - 1]          # full tiles, not the first of a row
-names = ["issue + stage ctrl + barrier 1", "phase A (next tile)", "look-back (wave 0)", "barrier 2", "phase B + stores", "barrier 3"]
+names = ["issue + stage ctrl (wave-private: no barrier)", "phase A (next tile)", "look-back (wave 3)", "the barrier", "phase B + stores"]
+NS = len(names)                                        # stamp NS closes the iteration
 print("s_memtime ticks = shader cycles; one loop iteration = phase A of the next tile + look-back and phase B of this one; mean per wave")
 if not V2:
     # wave tiles: a tile carries the stamps of the one wave that rendered it
@@ -38,9 +39,9 @@ if not V2:
     print(f"kernel span {(flat[:, 11].max() - flat[:, 10].min()).item() / 100:.1f} us")
     sys.exit(0)
 for w in range(4):
-    d = [(st[:, :, w, i + 1] - st[:, :, w, i]).mean().item() for i in range(6)]
-    print(f"wave {w}: " + ", ".join(f"{n} {x:.0f}" for n, x in zip(names, d)) + f"; iteration {(st[:, :, w, 6] - st[:, :, w, 0]).mean().item():.0f} cycles")
-cyc = (st[:, :, 0, 6] - st[:, :, 0, 0])
+    d = [(st[:, :, w, i + 1] - st[:, :, w, i]).mean().item() for i in range(NS)]
+    print(f"wave {w}: " + ", ".join(f"{n} {x:.0f}" for n, x in zip(names, d)) + f"; iteration {(st[:, :, w, NS] - st[:, :, w, 0]).mean().item():.0f} cycles")
+cyc = (st[:, :, 0, NS] - st[:, :, 0, 0])
 real = (st[:, :, 0, 11] - st[:, :, 0, 10])           # s_memrealtime: 100 MHz
 print(f"in-kernel clock = {cyc.sum().item() / real.sum().item() * 0.1:.3f} GHz")
 span_real = (st[:, :, :, 11].max() - st[:, :, :, 10].min()).item()
