@@ -380,6 +380,51 @@ int ias_l1_cdist(const float* queries, const float* bank, int N, int M, long lon
 int ias_topk_merge(const float* dist, int N, int M, long long ld, long long base, int k, float* best_dist,
                    long long* best_idx, void* stream);
 
+/* ---- Evolutionary search stage of sound matching (evolve.evolve_search): an elitist cross-entropy search per sound,
+ * scored with ias_l1_cdist and selected with ias_topk_merge.  The reference fits parameters by descent through mel-L1 alone
+ * (its audio_to_params.py:56-172); a population search is the classic tool for synthesiser sound matching.
+ * ias_evolve_sample: out [N, M, P] (device fp32) = a population of M candidates per sound drawn around mean [N, P] with the
+ *   spread sigma [N, P] (device fp32); free_cols [P] (device uint8) marks the columns that vary.  With n' = n_base + n and
+ *   m' = m_base + m:
+ *     a frozen column (free_cols[j] == 0):  out[n,m,j] = mean[n,j], the same bits;
+ *     a free column:  out[n,m,j] = clamp(mean[n,j] + sigma[n,j] z, 0, 1) in fp32: one multiply rounded, one add rounded (no
+ *       FMA), then x < 0 ? 0 : x > 1 ? 1 : x (a NaN stays a NaN).
+ *   z is a standard normal from Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants
+ *   0x9E3779B9, 0xBB67AE85) with key = (seed & 0xffffffff, seed >> 32) and counter = (m', n', generation, j >> 2): the four
+ *   output words x0..x3 serve columns 4 (j >> 2) + 0..3.  u(x) = ((x >> 9) + 0.5) 2^-23, exact in fp32 and inside (0, 1);
+ *   z0 = sqrt(-2 ln u(x0)) cos(2 pi u(x1)), z1 = sqrt(-2 ln u(x0)) sin(2 pi u(x1)), z2 and z3 the same from (x2, x3); in
+ *   fp32 with the accurate logf (no fast intrinsic), a correctly rounded sqrtf and multiply, and cospif / sinpif of the
+ *   exact 2 u.  |z| <= sqrt(-2 ln 2^-24) = 5.77.  A value depends on (seed, generation, n', m', j), mean[n,j] and
+ *   sigma[n,j] alone: not on N, M, the launch shape or how a population is cut into calls through n_base and m_base.
+ *   One launch.  IAS_ERR_ARG: null pointers, N, M or P < 1, P > 128, n_base < 0, m_base < 0, generation < 0.
+ *   IAS_ERR_UNSUPPORTED: n_base + N > 2^32, m_base + M > 2^32 or generation >= 2^32 (a counter word has 32 bits).
+ *   Nothing is launched on a refusal.
+ * ias_evolve_update: called after ias_topk_merge has merged the generation whose candidates pop [N, M, P] have the global
+ *   indices base + m into elite_dist / elite_idx [N, k]; prev_idx [N, k] and prev_params [N, k, P] are the elite indices
+ *   and parameters from before that merge.  It gathers the elites' parameters and refits the sampling distribution.
+ *   Gather, elite_params[n,e,:] (device fp32 [N, k, P], not the same buffer as prev_params):
+ *     base <= elite_idx[n,e] < base + M:            the bits of pop[n, elite_idx[n,e] - base, :];
+ *     else elite_idx[n,e] == prev_idx[n,s]:         the bits of prev_params[n,s,:] (the lowest such s);
+ *     elite_idx[n,e] == INT64_MAX (an empty slot):  +0;
+ *     found nowhere (a caller's bug):               NaN.
+ *   Update: E = the slots e with a finite elite_dist[n,e] and a non-empty index, in slot order, c = |E|.  c == 0: mean[n,:]
+ *   and sigma[n,:] keep their bits.  Otherwise, per free column j in fp64 without contraction, x_e = elite_params[n,e,j]:
+ *     mu = (sum_E x_e) / c, v = (sum_E (x_e - mu)^2) / c, both sums from 0 in slot order;
+ *     mean[n,j]  = fp32(clamp((1 - alpha) mean[n,j] + alpha mu, 0, 1));
+ *     sigma[n,j] = fp32(min(sigma_max, max(sigma_min, (1 - alpha) sigma[n,j] + alpha sqrt(v))));
+ *   (clamps as comparisons: a NaN stays a NaN) and frozen columns keep the bits of mean and sigma.  mean and sigma (device
+ *   fp32 [N, P]) are rewritten in place.  One launch, one workgroup per sound, a lane per column, no atomics.
+ *   IAS_ERR_ARG: null pointers, N, M, k or P < 1, k > 64, P > 128, base < 0, alpha outside [0, 1], sigma_min or sigma_max
+ *   not finite, sigma_min < 0, sigma_max < sigma_min, elite_params == prev_params.  IAS_ERR_UNSUPPORTED: N > 65535.
+ *   Nothing is launched on a refusal. */
+int ias_evolve_sample(const float* mean, const float* sigma, const unsigned char* free_cols, int N, int M, int P,
+                      int n_base, long long m_base, unsigned long long seed, long long generation, float* out,
+                      void* stream);
+int ias_evolve_update(const float* pop, long long base, int M, const float* elite_dist, const long long* elite_idx,
+                      const long long* prev_idx, const float* prev_params, float* elite_params, float* mean, float* sigma,
+                      const unsigned char* free_cols, int N, int k, int P, double alpha, double sigma_min,
+                      double sigma_max, void* stream);
+
 /* ---- Band-limited resampling (resample.resample / resample.Resample, match_audio.py --resample): torchaudio's
  * windowed-sinc polyphase resampler, torchaudio.functional.resample (_get_sinc_resample_kernel +
  * _apply_sinc_resample_kernel), which the reference depends on (its requirements.txt).

@@ -92,6 +92,9 @@ SYMBOLS = {
     "ias_l1_cdist_workspace_bytes": (_LL, [_I, _I, _LL]),
     "ias_l1_cdist": (_I, [_P, _P, _I, _I, _LL, _P, _P, _P]),
     "ias_topk_merge": (_I, [_P, _I, _I, _LL, _LL, _I, _P, _P, _P]),
+    "ias_evolve_sample": (_I, [_P, _P, _P, _I, _I, _I, _I, _LL, _c.c_ulonglong, _LL, _P, _P]),
+    "ias_evolve_update": (_I, [_P, _LL, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _c.c_double, _c.c_double,
+                              _c.c_double, _P]),
     "ias_resample_plan": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
     "ias_resample_build_taps": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
     "ias_resample_out_len": (_LL, [_LL, _I, _I]),

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from . import voice_spec as S
+from .evolve import EvolveResult, evolve_search  # noqa: F401  (the search stage, exported beside the fit)
 from .spectral import MelSpectrogramL1, MultiResolutionSTFTLoss, STFTL1
 
 LOSSES = ("mel_l1", "stft_l1", "multi_resolution_stft")
@@ -88,6 +89,7 @@ class SoundMatcher:
         for k in frozen:
             if k not in S.INDEX:
                 raise KeyError(f"unknown Voice parameter {k}")
+        self.frozen = tuple(frozen)
         self.free = torch.tensor([k not in frozen for k in keys], dtype=torch.uint8, device=voice.params01.device)
 
     def _per_item(self, audio, target):
@@ -96,6 +98,13 @@ class SoundMatcher:
         if self.loss_kind == "multi_resolution_stft":
             return self.loss.per_item(audio, targets=target)
         return self.loss.per_item(audio, target_values=target)
+
+    def search(self, target_audio, **kw):
+        """``evolve.evolve_search`` on this matcher's voice with its loss and frozen set (``kw``: generations, population,
+        elites, init_params01, sigma0, alpha, sigma_min, sigma_max, seed) -> ``EvolveResult``; its ``params01[:, :S]`` are
+        starts for ``fit(init_params01=...)``.  The multi-resolution loss is refused as by ``SpectralBank``: search with a
+        mel matcher's loss through ``evolve_search`` instead."""
+        return evolve_search(self.voice, self.loss, target_audio=target_audio, frozen=self.frozen, **kw)
 
     def fit(self, target_audio, init_params01=None, steps=200, return_audio=False):
         """target_audio [N, T] (device, T == voice.synthconfig.buffer_size); init_params01 [N, 78] in 0..1 (None: 0.5)

@@ -2,7 +2,8 @@
 """Sound matching entry point: fit the 78 Voice parameters to WAV files.
 
     python match_audio.py in1.wav in2.wav --steps 200 --out DIR [--init center|random|bank] [--starts S]
-                          [--bank-batches NB] [--bank-stream CHUNK] [--loss LOSS] [key=value ...]
+                          [--bank-batches NB] [--bank-stream CHUNK] [--evolve G] [--evolve-population M]
+                          [--evolve-elites K] [--evolve-sigma S0] [--loss LOSS] [key=value ...]
 
 ``key=value`` are config overrides as for pretrain.py / audio_to_params.py (``torchsynth.rate``,
 ``torchsynth.buffer_size_seconds``, ``mel.*``); the matcher's own settings are flags.  Input WAVs are 16-, 24- or 32-bit
@@ -16,7 +17,12 @@ whose 1.1 ms hop constrains the envelopes' short segments better).  ``--init``: 
 and each sound starts from its ``--starts`` nearest voices under the matcher's loss (a mel bank for
 multi_resolution_stft); the best start is kept and the JSON record names it (``bank_index``, ``bank_distance``).  With
 ``--bank-stream CHUNK`` the bank is not kept: ``SpectralBank.search`` renders it CHUNK batches at a time and keeps the
-running nearest voices, with the same result, so ``--bank-batches`` is bounded by time and not by memory."""
+running nearest voices, with the same result, so ``--bank-batches`` is bounded by time and not by memory.
+``--evolve G`` (default 0: off) puts an evolutionary search between the start and the fit: ``evolve.evolve_search`` runs G
+generations of ``--evolve-population`` candidates per sound (a multiple of 128) from the starts ``--init`` produced, with
+the same loss as the bank and ``--seed``; its ``--starts`` best of ``--evolve-elites`` elites become the Adam starts (so
+``--starts`` may exceed 1 with ``--init center``), and the JSON record names the kept one (``evolve_index``,
+``evolve_distance``) in place of the bank voice."""
 import argparse
 import json
 import os
@@ -136,7 +142,14 @@ def parse_args(argv=None):
     ap.add_argument("--beta2", type=float, default=0.999)
     ap.add_argument("--eps", type=float, default=1e-8)
     ap.add_argument("--batch-size", type=int, default=128, help="sounds fitted at once (at most)")
-    ap.add_argument("--seed", type=int, default=0, help="seed of --init random")
+    ap.add_argument("--seed", type=int, default=0, help="seed of --init random and of --evolve")
+    ap.add_argument("--evolve", type=int, default=0, metavar="G",
+                    help="generations of evolutionary search between the start and the fit (0: none)")
+    ap.add_argument("--evolve-population", type=int, default=4 * BANK_BATCH, metavar="M",
+                    help="--evolve: candidates per sound and generation, a multiple of 128")
+    ap.add_argument("--evolve-elites", type=int, default=8, metavar="K", help="--evolve: elites kept per sound (1..64)")
+    ap.add_argument("--evolve-sigma", type=float, default=0.2, metavar="S0",
+                    help="--evolve: initial standard deviation of every free parameter")
     ap.add_argument("--resample", action="store_true",
                     help="read files at any rate and resample them to torchsynth.rate on the device; NAME.match.wav is "
                          "written at the input's rate")
@@ -147,7 +160,20 @@ def parse_args(argv=None):
         ap.error("no input WAV files")
     if args.starts < 1:
         ap.error("--starts must be >= 1")
-    if args.init == "center" and args.starts != 1:
+    if args.evolve < 0:
+        ap.error("--evolve must be >= 0")
+    if args.evolve_population < 1 or args.evolve_population % BANK_BATCH != 0:
+        ap.error(f"--evolve-population must be a positive multiple of {BANK_BATCH}")
+    if not 1 <= args.evolve_elites <= 64:
+        ap.error("--evolve-elites must be in 1..64")
+    if not 0.0 <= args.evolve_sigma < float("inf"):
+        ap.error("--evolve-sigma must be finite and >= 0")
+    if args.evolve > 0:
+        if args.starts > args.evolve_elites:
+            ap.error("--evolve: --starts must not exceed --evolve-elites")
+        if args.evolve_population > (1 << 31) // args.evolve:
+            ap.error("--evolve: --evolve-population x --evolve must not exceed 2^31")
+    if args.init == "center" and args.starts != 1 and args.evolve == 0:
         ap.error("--init center has one start per sound: --starts must be 1")
     if args.bank_batches < 1:
         ap.error("--bank-batches must be >= 1")
@@ -185,7 +211,7 @@ def main(argv=None):
     matcher = SoundMatcher(voice, loss=args.loss, mel_kwargs=dict(cfg.mel), lr=args.lr, betas=(args.beta1, args.beta2),
                            eps=args.eps)
     N, nS = len(files), args.starts
-    bank_idx = bank_dist = None
+    bank_idx = bank_dist = bank_voice = None
     if args.init == "random":
         init = torch.rand((N * nS, 78), generator=torch.Generator().manual_seed(args.seed)).to(dev)
         init = init.reshape(N, nS, 78) if nS > 1 else init
@@ -220,6 +246,30 @@ def main(argv=None):
             del bank
     else:
         init = None
+    evolve_idx = evolve_dist = None
+    if args.evolve > 0:
+        from inverse_audio_synthesis_amd.evolve import evolve_search
+        if bank_voice is None:
+            bank_voice = Voice(SynthConfig(batch_size=BANK_BATCH, sample_rate=rate,
+                                           buffer_size_seconds=cfg.torchsynth.buffer_size_seconds,
+                                           reproducible=cfg.torchsynth.reproducible)).to(dev)
+            if args.loss == "multi_resolution_stft":
+                from inverse_audio_synthesis_amd.spectral import MelSpectrogramL1
+                kw = dict(cfg.mel)
+                kw.setdefault("sample_rate", rate)
+                bank_loss = MelSpectrogramL1(**kw).to(dev)
+            else:
+                bank_loss = matcher.loss
+        print(f"match_audio.py: evolutionary search, {args.evolve} generations of {args.evolve_population} candidates per "
+              f"sound, {args.evolve_elites} elites", flush=True)
+        found = evolve_search(bank_voice, bank_loss, target_audio=target, generations=args.evolve,
+                              population=args.evolve_population, elites=args.evolve_elites, init_params01=init,
+                              sigma0=args.evolve_sigma, seed=args.seed)
+        nS = args.starts
+        evolve_idx, evolve_dist = found.idx[:, :nS], found.dist[:, :nS]
+        init = found.params01[:, :nS].contiguous() if nS > 1 else found.params01[:, 0].contiguous()
+        bank_idx = bank_dist = None                      # the kept start is an elite, no longer a bank voice
+        del found
     res = matcher.fit(target, init_params01=init, steps=args.steps, return_audio=True)
     os.makedirs(args.out, exist_ok=True)
     if args.resample:
@@ -243,6 +293,11 @@ def main(argv=None):
             s = int(res.start[i]) if res.start is not None else 0
             rec["bank_index"] = int(bank_idx[i, s])
             rec["bank_distance"] = float(bank_dist[i, s])
+        if evolve_idx is not None:
+            s = int(res.start[i]) if res.start is not None else 0
+            rec["evolve_generations"], rec["evolve_population"] = args.evolve, args.evolve_population
+            rec["evolve_index"] = int(evolve_idx[i, s])
+            rec["evolve_distance"] = float(evolve_dist[i, s])
         if args.resample:
             rec["input_rate"], rec["synth_rate"] = int(in_rates[i]), rate
         with open(os.path.join(args.out, name + ".params.json"), "w") as fh:
