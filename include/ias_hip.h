@@ -425,6 +425,38 @@ int ias_evolve_update(const float* pop, long long base, int M, const float* elit
                       const unsigned char* free_cols, int N, int k, int P, double alpha, double sigma_min,
                       double sigma_max, void* stream);
 
+/* ---- Pitch estimation of the targets of sound matching (pitch.pitch_yin / pitch.estimate_pitch, match_audio.py --pitch):
+ * YIN (de Cheveigne & Kawahara 2002: cumulative-mean-normalised difference function, absolute threshold, parabolic
+ * refinement).  The reference never analyses its targets, so this has no counterpart there.
+ * ias_pitch_frames (HOST only): F = (T - W - tau_max) / hop + 1 (integer division), the number of frames of a row; a
+ *   negative IAS_ERR_ARG when a size is < 1 or T < W + tau_max (not even one frame).
+ * ias_pitch_yin: audio [B, T] (device fp32, row-major, row stride T) -> period, aperiodicity, energy [B, F] and, when
+ *   dprime is not NULL, dprime [B, F, tau_max + 1] (all device fp32).  Frame f of row b starts at s = f hop and uses
+ *   x[s .. s + W + tau_max).  Per-frame contract (as ias_resample / ias_l1_rows fix their chains):
+ *     d(tau), tau = 1 .. tau_max: one fp32 chain over j = 0 .. W - 1 in that order from +0,
+ *       acc = fmaf(x[s+j] - x[s+j+tau], x[s+j] - x[s+j+tau], acc) (the difference rounded to fp32 first);
+ *     energy: the same chain over x[s+j]^2, acc = fmaf(x[s+j], x[s+j], acc);
+ *     c(tau) = sum_{k <= tau} d(k) in fp64, added in tau order from 0;
+ *     d'(0) = 1; d'(tau) = fp32(d(tau) tau / c(tau)), product and quotient in fp64, rounded to fp32 once; d'(tau) = 1
+ *       where c(tau) == 0;
+ *     pick, on the fp32 d': the smallest tau in [tau_min, tau_max] with d'(tau) < threshold, then forward while
+ *       tau + 1 <= tau_max and d'(tau + 1) < d'(tau); when no tau is under the threshold, the first global minimum of d'
+ *       over [tau_min, tau_max];
+ *     aperiodicity = d'(tau_pick), the same bits;
+ *     period: with y0, y1, y2 = d'(tau - 1), d'(tau), d'(tau + 1) in fp64, when tau_min < tau_pick < tau_max and
+ *       y0 - 2 y1 + y2 > 0: fp32(tau + (y0 - y2) / (2 (y0 - 2 y1 + y2))), formed in fp64 and rounded once; else tau.
+ *   A frame's outputs depend on its W + tau_max samples and the scalar arguments alone: not on B, the row's position, its
+ *   alignment or the launch shape.  One launch (one workgroup per frame and row), no workspace, no atomics on global
+ *   memory, no global state: capturable.
+ *   IAS_ERR_ARG: null pointers (dprime may be NULL), B, T, W or hop < 1, tau_min < 2, tau_min > tau_max, T < W + tau_max,
+ *   a threshold outside (0, 1] (a NaN included).  IAS_ERR_UNSUPPORTED: a frame over the kernel's LDS budget of 64 KB,
+ *   8 (tau_max + 1) + 4 (W + tau_max + 8) + 4 (tau_max + 1) > 65536 bytes (the fp64 running sum, the frame and its zero
+ *   padding, d; W = tau_max fits up to 3274, a piano's lowest note at 90 kHz); B > 65535; with dprime, B F (tau_max + 1) >
+ *   INT_MAX (dprime is a diagnostic output whose element index is an int).  Nothing is launched on a refusal. */
+long long ias_pitch_frames(int T, int W, int tau_max, int hop);
+int ias_pitch_yin(const float* audio, int B, int T, int W, int tau_min, int tau_max, int hop, float threshold,
+                  float* period, float* aperiodicity, float* energy, float* dprime, void* stream);
+
 /* ---- Band-limited resampling (resample.resample / resample.Resample, match_audio.py --resample): torchaudio's
  * windowed-sinc polyphase resampler, torchaudio.functional.resample (_get_sinc_resample_kernel +
  * _apply_sinc_resample_kernel), which the reference depends on (its requirements.txt).

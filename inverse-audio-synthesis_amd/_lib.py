@@ -95,6 +95,8 @@ SYMBOLS = {
     "ias_evolve_sample": (_I, [_P, _P, _P, _I, _I, _I, _I, _LL, _c.c_ulonglong, _LL, _P, _P]),
     "ias_evolve_update": (_I, [_P, _LL, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _c.c_double, _c.c_double,
                               _c.c_double, _P]),
+    "ias_pitch_frames": (_LL, [_I, _I, _I, _I]),
+    "ias_pitch_yin": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     "ias_resample_plan": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
     "ias_resample_build_taps": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
     "ias_resample_out_len": (_LL, [_LL, _I, _I]),

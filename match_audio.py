@@ -3,7 +3,8 @@
 
     python match_audio.py in1.wav in2.wav --steps 200 --out DIR [--init center|random|bank] [--starts S]
                           [--bank-batches NB] [--bank-stream CHUNK] [--evolve G] [--evolve-population M]
-                          [--evolve-elites K] [--evolve-sigma S0] [--loss LOSS] [key=value ...]
+                          [--evolve-elites K] [--evolve-sigma S0] [--pitch] [--pitch-lo MIDI] [--pitch-hi MIDI]
+                          [--loss LOSS] [key=value ...]
 
 ``key=value`` are config overrides as for pretrain.py / audio_to_params.py (``torchsynth.rate``,
 ``torchsynth.buffer_size_seconds``, ``mel.*``); the matcher's own settings are flags.  Input WAVs are 16-, 24- or 32-bit
@@ -22,7 +23,11 @@ running nearest voices, with the same result, so ``--bank-batches`` is bounded b
 generations of ``--evolve-population`` candidates per sound (a multiple of 128) from the starts ``--init`` produced, with
 the same loss as the bank and ``--seed``; its ``--starts`` best of ``--evolve-elites`` elites become the Adam starts (so
 ``--starts`` may exceed 1 with ``--init center``), and the JSON record names the kept one (``evolve_index``,
-``evolve_distance``) in place of the bank voice."""
+``evolve_distance``) in place of the bank voice.
+``--pitch`` (off by default) listens to the targets first: ``pitch.estimate_pitch`` reads each target's note between
+``--pitch-lo`` and ``--pitch-hi`` (MIDI, default 21..108) off the waveform and ``pitch.retune`` moves ``keyboard.midi_f0``
+of every start ``--init`` produced onto it, before ``--evolve`` and the fit; unvoiced targets keep their starts.  The
+JSON record gains ``estimated_midi`` (null when unvoiced), ``voiced`` and ``pitch_confidence``."""
 import argparse
 import json
 import os
@@ -153,6 +158,10 @@ def parse_args(argv=None):
     ap.add_argument("--resample", action="store_true",
                     help="read files at any rate and resample them to torchsynth.rate on the device; NAME.match.wav is "
                          "written at the input's rate")
+    ap.add_argument("--pitch", action="store_true",
+                    help="estimate each target's note and start keyboard.midi_f0 there (pitch.estimate_pitch / retune)")
+    ap.add_argument("--pitch-lo", type=float, default=21.0, metavar="MIDI", help="--pitch: lowest note searched")
+    ap.add_argument("--pitch-hi", type=float, default=108.0, metavar="MIDI", help="--pitch: highest note searched")
     args = ap.parse_args(argv)
     files = [a for a in args.inputs if "=" not in a]
     overrides = [a for a in args.inputs if "=" in a]
@@ -175,6 +184,8 @@ def parse_args(argv=None):
             ap.error("--evolve: --evolve-population x --evolve must not exceed 2^31")
     if args.init == "center" and args.starts != 1 and args.evolve == 0:
         ap.error("--init center has one start per sound: --starts must be 1")
+    if not args.pitch_lo < args.pitch_hi:
+        ap.error("--pitch-lo must be below --pitch-hi")
     if args.bank_batches < 1:
         ap.error("--bank-batches must be >= 1")
     if args.bank_stream is not None:
@@ -246,6 +257,16 @@ def main(argv=None):
             del bank
     else:
         init = None
+    pitch = None
+    if args.pitch:
+        from inverse_audio_synthesis_amd.pitch import estimate_pitch, retune
+        try:
+            pitch = estimate_pitch(target, rate, midi_lo=args.pitch_lo, midi_hi=args.pitch_hi)
+        except ValueError as e:
+            sys.exit(f"match_audio.py: --pitch: {e}")
+        if init is None:                                 # --init center: the centre matrix, so that it can be retuned
+            init = torch.full((N, 78), 0.5, dtype=torch.float32, device=dev)
+        init = retune(init, pitch)
     evolve_idx = evolve_dist = None
     if args.evolve > 0:
         from inverse_audio_synthesis_amd.evolve import evolve_search
@@ -298,6 +319,10 @@ def main(argv=None):
             rec["evolve_generations"], rec["evolve_population"] = args.evolve, args.evolve_population
             rec["evolve_index"] = int(evolve_idx[i, s])
             rec["evolve_distance"] = float(evolve_dist[i, s])
+        if pitch is not None:
+            rec["voiced"] = bool(pitch.voiced[i])
+            rec["estimated_midi"] = float(pitch.midi[i]) if rec["voiced"] else None
+            rec["pitch_confidence"] = float(pitch.confidence[i])
         if args.resample:
             rec["input_rate"], rec["synth_rate"] = int(in_rates[i]), rate
         with open(os.path.join(args.out, name + ".params.json"), "w") as fh:
