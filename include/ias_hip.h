@@ -457,6 +457,57 @@ long long ias_pitch_frames(int T, int W, int tau_max, int hop);
 int ias_pitch_yin(const float* audio, int B, int T, int W, int tau_min, int tau_max, int hop, float threshold,
                   float* period, float* aperiodicity, float* energy, float* dprime, void* stream);
 
+/* ---- Onset detection and note segmentation of the targets of sound matching (onset.detect_onsets / split_notes /
+ * join_notes, match_audio.py --split): spectral flux of the log-compressed mel spectrogram, a peak picker, and the two
+ * copies between a recording and one synth buffer per note.  The reference never analyses its targets, so this has no
+ * counterpart there.  Every entry: one launch, no workspace, no atomics on global memory, no global state: capturable.
+ * Nothing is launched on a refusal.
+ * ias_onset_flux: mel [B, F, M] (device fp32, frames-major, the power values of ias_stft) -> flux [B, F] and, when logmel
+ *   is not NULL, logmel [B, F, M] (device fp32; a diagnostic output).
+ *     L(b,f,m) = fp32(log1p((double)gamma * (double)mel[b,f,m])): the product and the log in fp64, rounded to fp32 once;
+ *       L = +0 for f < 0 (the row is preceded by silence, so a note sounding at sample 0 is an onset);
+ *     flux[b,f] = fp32((sum_m p((double)L(b,f,m) - (double)L(b,f-lag,m))) / M), p(x) = x > 0 ? x : 0 (a comparison: a NaN
+ *       difference adds 0), the sum one fp64 chain in ascending m from +0, divided by M in fp64, rounded to fp32 once.
+ *       Each fp64 difference of two fp32 values is exact.
+ *   A frame's bits depend on its own 2 M inputs and the scalars alone: not on B, the row, the alignment or the launch
+ *   shape.  IAS_ERR_ARG: null pointers (logmel may be NULL), B, F, M or lag < 1, gamma not finite or <= 0.
+ *   IAS_ERR_UNSUPPORTED: B ceil(F / 16) > INT_MAX (the grid).
+ * ias_onset_pick: flux [B, F] (device fp32) -> frames [B, K] (int32), strength [B, K] (fp32), count [B] (int32).  Per row,
+ *   on the fp32 flux x, every window clipped to [0, F - 1]:
+ *     frame f is a candidate when x[f] >= x[g] for every g in [f - pre_max, f + post_max] and
+ *       (double)x[f] >= s / n + (double)delta, s one fp64 chain over x[g], g ascending in [f - pre_avg, f + post_avg], from
+ *       +0, n its number of terms; the division first, then the addition, both in fp64.  Comparisons as written: a NaN is
+ *       never a candidate and defeats the first condition of the frames whose window holds it;
+ *     candidates are walked in ascending f; one is accepted when none has been accepted yet or f - last_accepted > wait;
+ *     the accepted frames in ascending order: the first K go to frames and the bits of their flux to strength, unused
+ *       slots get -1 and +0; count = the number accepted, which may exceed K.
+ *   One workgroup per row: windows and candidate flags in parallel over frames, the greedy walk serial over the compacted
+ *   candidates.  A row's outputs do not depend on B or on its position.
+ *   IAS_ERR_ARG: null pointers, B, F or K < 1, a negative window size or wait, delta not > 0 (a NaN included: without a
+ *   positive delta silence is one long plateau of candidates).  IAS_ERR_UNSUPPORTED: B > 65535.
+ * ias_segment_gather: audio [N, L] (device fp32) and S segments (row, start, length: int32 [S]; faded: uint8 [S]) ->
+ *   out [S, T] (device fp32).  For t < min(length[s], T): x = audio[row[s], start[s] + t], 0 when row[s] is outside [0, N)
+ *   or start[s] + t outside [0, L) (nothing there is read);  out[s,t] = the bits of x, except where faded[s] != 0 and
+ *   t >= length[s] - fade: fp32(x * fp32((float)(length[s] - t) * inv_fade)), a linear fade-out over the note's last
+ *   `fade` samples; inv_fade is 1.0f / fade, computed by the caller (unused with fade == 0).  Elsewhere out[s,t] = +0.
+ *   A lane stores one 16-byte-aligned group of four samples; its load is one 16-byte load when start[s] puts the source
+ *   at the same 16-byte phase, four 4-byte loads otherwise.
+ * ias_segment_scatter: the inverse.  notes [S, T], gain fp32 [S] -> out [N, L]: for t < min(length[s], T) with row[s] in
+ *   [0, N) and start[s] + t in [0, L): out[row[s], start[s] + t] = fp32(fp32(notes[s,t] * gain[s]) * g), g the fade
+ *   factor above, the second product left out where there is no fade.  Nothing else of out is written: the caller zeroes
+ *   it first, and guarantees that segments do not overlap (onset.split_notes builds them so); then the result is
+ *   deterministic.
+ *   Both: IAS_ERR_ARG: null pointers, N, L, S or T < 1, fade < 0, inv_fade not finite.  IAS_ERR_UNSUPPORTED:
+ *   T > INT_MAX - 2048 or S ceil((T / 4 + 2) / 256) > INT_MAX (the grid). */
+int ias_onset_flux(const float* mel, int B, int F, int M, int lag, float gamma, float* flux, float* logmel, void* stream);
+int ias_onset_pick(const float* flux, int B, int F, int pre_max, int post_max, int pre_avg, int post_avg, float delta,
+                   int wait, int K, int* frames, float* strength, int* count, void* stream);
+int ias_segment_gather(const float* audio, int N, int L, const int* row, const int* start, const int* length,
+                       const unsigned char* faded, int S, int T, int fade, float inv_fade, float* out, void* stream);
+int ias_segment_scatter(const float* notes, int N, int L, const int* row, const int* start, const int* length,
+                        const unsigned char* faded, int S, int T, int fade, float inv_fade, const float* gain, float* out,
+                        void* stream);
+
 /* ---- Band-limited resampling (resample.resample / resample.Resample, match_audio.py --resample): torchaudio's
  * windowed-sinc polyphase resampler, torchaudio.functional.resample (_get_sinc_resample_kernel +
  * _apply_sinc_resample_kernel), which the reference depends on (its requirements.txt).

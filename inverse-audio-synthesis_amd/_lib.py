@@ -97,6 +97,10 @@ SYMBOLS = {
                               _c.c_double, _P]),
     "ias_pitch_frames": (_LL, [_I, _I, _I, _I]),
     "ias_pitch_yin": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "ias_onset_flux": (_I, [_P, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "ias_onset_pick": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P]),
+    "ias_segment_gather": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P]),
+    "ias_segment_scatter": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P]),
     "ias_resample_plan": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
     "ias_resample_build_taps": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
     "ias_resample_out_len": (_LL, [_LL, _I, _I]),

@@ -4,7 +4,9 @@ An L1 spectral loss has almost no gradient along ``keyboard.midi_f0`` (partials 
 fit has to *start* within a partial's width of the target's note.  The fundamental can be read off
 the waveform: ``pitch_yin`` (ias_pitch_yin, csrc/pitch_kernels.hip) runs de Cheveigne & Kawahara's YIN per frame,
 ``aggregate_pitch`` turns the frames of a sound into one MIDI note, a voiced flag and a confidence, and ``retune`` moves the
-keyboard of a start onto that note (``match_audio.py --pitch``).  One note per sound is assumed.
+keyboard of a start onto that note (``match_audio.py --pitch``).  One note per sound is assumed; a
+recording of several notes is cut into one sound per note first (``onset.detect_onsets`` / ``split_notes``,
+``match_audio.py --split``).
 """
 import math
 from dataclasses import dataclass

@@ -4,7 +4,7 @@
     python match_audio.py in1.wav in2.wav --steps 200 --out DIR [--init center|random|bank] [--starts S]
                           [--bank-batches NB] [--bank-stream CHUNK] [--evolve G] [--evolve-population M]
                           [--evolve-elites K] [--evolve-sigma S0] [--pitch] [--pitch-lo MIDI] [--pitch-hi MIDI]
-                          [--loss LOSS] [key=value ...]
+                          [--split] [--onset-delta D] [--max-notes K] [--fade-ms MS] [--loss LOSS] [key=value ...]
 
 ``key=value`` are config overrides as for pretrain.py / audio_to_params.py (``torchsynth.rate``,
 ``torchsynth.buffer_size_seconds``, ``mel.*``); the matcher's own settings are flags.  Input WAVs are 16-, 24- or 32-bit
@@ -27,7 +27,15 @@ the same loss as the bank and ``--seed``; its ``--starts`` best of ``--evolve-el
 ``--pitch`` (off by default) listens to the targets first: ``pitch.estimate_pitch`` reads each target's note between
 ``--pitch-lo`` and ``--pitch-hi`` (MIDI, default 21..108) off the waveform and ``pitch.retune`` moves ``keyboard.midi_f0``
 of every start ``--init`` produced onto it, before ``--evolve`` and the fit; unvoiced targets keep their starts.  The
-JSON record gains ``estimated_midi`` (null when unvoiced), ``voiced`` and ``pitch_confidence``."""
+JSON record gains ``estimated_midi`` (null when unvoiced), ``voiced`` and ``pitch_confidence``.
+``--split`` (off by default) matches a recording note by note.  The files are read whole (after ``--resample``),
+``onset.detect_onsets`` finds every file's note onsets on the device (``--onset-delta``; at most ``--max-notes`` per file,
+with a warning when there are more) and ``onset.split_notes`` cuts one synth buffer per note from its onset, faded out over
+``--fade-ms`` where the next note or the end of the buffer cuts it.  ``--pitch``, ``--init``, ``--evolve`` and the fit then
+see the notes exactly as they see files.  Per input NAME the script writes NAME.notes.json ({input, rate, notes}: per
+note ``onset_sample``, ``onset_seconds``, ``length_samples``, ``strength``, ``gain`` and the fields of a params.json record)
+and NAME.match.wav at the file's full length: the best renders, each scaled by ``gain`` (the RMS of the target note over
+the RMS of its render) and put back at its onset (``onset.join_notes``)."""
 import argparse
 import json
 import os
@@ -126,6 +134,93 @@ def params_record(params01_row):
             for i, (m, n, *_r) in enumerate(S.PARAMS)]
 
 
+def split_targets(files, rate, T, args, dev):
+    """--split: read every file whole (with --resample at its own rate, brought to ``rate`` on the device), zero-pad to the
+    longest, find the onsets and cut one buffer of ``T`` samples per note.  -> (``onset.NoteSegments`` with S notes, the
+    padded recordings [N, L] at ``rate``, the files' rates, their lengths in samples at their own rates)."""
+    import torch
+    from inverse_audio_synthesis_amd.onset import detect_onsets, split_notes
+    read = [read_wav_any_rate(f) for f in files]
+    in_rates = [sr for _x, sr in read]
+    in_lengths = [len(x) for x, _sr in read]
+    rows = [None] * len(files)
+    if args.resample:
+        from inverse_audio_synthesis_amd.resample import resample, resample_plan, output_length
+        for sr in sorted(set(in_rates)):
+            idx = [i for i, r in enumerate(in_rates) if r == sr]
+            x = np.zeros((len(idx), max(in_lengths[i] for i in idx)), dtype=np.float32)
+            for k, i in enumerate(idx):
+                x[k, :in_lengths[i]] = read[i][0]
+            y = resample(torch.from_numpy(x).to(dev), sr, rate)
+            o, n, _w, _K = resample_plan(sr, rate)
+            for k, i in enumerate(idx):
+                rows[i] = y[k, :output_length(in_lengths[i], o, n)]
+    else:
+        for i, (x, sr) in enumerate(read):
+            if sr != rate:
+                raise ValueError(f"{files[i]}: sample rate {sr} Hz, the synth runs at {rate} Hz (torchsynth.rate); pass "
+                                 f"--resample or torchsynth.rate={sr}")
+            rows[i] = torch.from_numpy(x).to(dev)
+    lengths = torch.tensor([int(r.numel()) for r in rows], dtype=torch.int64, device=dev)
+    whole = torch.zeros((len(rows), max(int(r.numel()) for r in rows)), dtype=torch.float32, device=dev)
+    for i, r in enumerate(rows):
+        whole[i, :r.numel()] = r
+    try:
+        onsets = detect_onsets(whole, rate, delta=args.onset_delta, max_onsets=args.max_notes)
+    except RuntimeError as e:
+        raise ValueError(f"--split: {e}")
+    for f, c in zip(files, onsets.count.tolist()):
+        if c > args.max_notes:
+            warnings.warn(f"{f}: {c} onsets, the first {args.max_notes} are kept (--max-notes)")
+    seg = split_notes(whole, lengths, onsets, T, int(round(args.fade_ms * 1e-3 * rate)))
+    print(f"match_audio.py: {seg.audio.shape[0]} notes in {len(files)} files", flush=True)
+    return seg, whole, in_rates, in_lengths
+
+
+def write_notes(args, files, rate, seg, whole, in_rates, in_lengths, renders, record):
+    """--split: NAME.notes.json and the full-length NAME.match.wav of every input."""
+    from inverse_audio_synthesis_amd.onset import join_notes, note_gains
+    gain = note_gains(seg.audio, renders, seg.length)
+    joined = join_notes(renders.contiguous(), seg, whole.shape[0], whole.shape[1], gain)
+    rows, starts, lengths = seg.row.tolist(), seg.start.tolist(), seg.length.tolist()
+    gains, strengths = gain.tolist(), seg.strength.tolist()
+    audio = [None] * len(files)
+    if args.resample:
+        from inverse_audio_synthesis_amd.resample import resample
+        for sr in sorted(set(in_rates)):
+            idx = [i for i, r in enumerate(in_rates) if r == sr]
+            back = resample(joined[idx].contiguous(), rate, sr).cpu().numpy()
+            for k, i in enumerate(idx):
+                audio[i] = fit_to(back[k], in_lengths[i])
+    else:
+        host = joined.cpu().numpy()
+        for i in range(len(files)):
+            audio[i] = host[i, :in_lengths[i]]
+    for i, f in enumerate(files):
+        name = os.path.splitext(os.path.basename(f))[0]
+        notes = []
+        for s in [s for s, r in enumerate(rows) if r == i]:
+            note = {"onset_sample": starts[s], "onset_seconds": starts[s] / rate, "length_samples": lengths[s],
+                    "strength": strengths[s], "gain": gains[s]}
+            note.update(record(s, os.path.basename(f)))
+            notes.append(note)
+        doc = {"input": os.path.basename(f), "rate": rate, "notes": notes}
+        if args.resample:
+            doc["input_rate"] = int(in_rates[i])
+        with open(os.path.join(args.out, name + ".notes.json"), "w") as fh:
+            json.dump(doc, fh, indent=1)
+        write_wav(os.path.join(args.out, name + ".match.wav"), audio[i], in_rates[i] if args.resample else rate)
+        print(json.dumps({"input": doc["input"], "notes": len(notes),
+                          "final_loss": [n["final_loss"] for n in notes]}), flush=True)
+
+
+def fit_to(x, length):
+    """Crop or zero-pad to ``length`` samples, silently (a resampled-back recording against the input's length)."""
+    if len(x) >= length:
+        return x[:length]
+    return np.concatenate([x, np.zeros(length - len(x), dtype=x.dtype)])
+
+
 INITS = ("center", "random", "bank")
 BANK_BATCH = 128
 
@@ -162,6 +257,14 @@ def parse_args(argv=None):
                     help="estimate each target's note and start keyboard.midi_f0 there (pitch.estimate_pitch / retune)")
     ap.add_argument("--pitch-lo", type=float, default=21.0, metavar="MIDI", help="--pitch: lowest note searched")
     ap.add_argument("--pitch-hi", type=float, default=108.0, metavar="MIDI", help="--pitch: highest note searched")
+    ap.add_argument("--split", action="store_true",
+                    help="find the note onsets of every file and match it note by note (onset.detect_onsets / split_notes); "
+                         "writes NAME.notes.json and a NAME.match.wav of the file's full length")
+    ap.add_argument("--onset-delta", type=float, default=0.2, metavar="D",
+                    help="--split: how far the spectral flux must rise above its moving mean at an onset")
+    ap.add_argument("--max-notes", type=int, default=256, metavar="K", help="--split: notes kept per file")
+    ap.add_argument("--fade-ms", type=float, default=5.0, metavar="MS",
+                    help="--split: linear fade-out of a note that is cut by the next onset or by the synth buffer")
     args = ap.parse_args(argv)
     files = [a for a in args.inputs if "=" not in a]
     overrides = [a for a in args.inputs if "=" in a]
@@ -186,6 +289,12 @@ def parse_args(argv=None):
         ap.error("--init center has one start per sound: --starts must be 1")
     if not args.pitch_lo < args.pitch_hi:
         ap.error("--pitch-lo must be below --pitch-hi")
+    if not 0.0 < args.onset_delta < float("inf"):
+        ap.error("--onset-delta must be finite and > 0")
+    if args.max_notes < 1:
+        ap.error("--max-notes must be >= 1")
+    if not 0.0 <= args.fade_ms < float("inf"):
+        ap.error("--fade-ms must be finite and >= 0")
     if args.bank_batches < 1:
         ap.error("--bank-batches must be >= 1")
     if args.bank_stream is not None:
@@ -208,12 +317,20 @@ def main(argv=None):
     cfg = load_config(os.path.join(ROOT, "conf"), "config", overrides)
     rate = int(cfg.torchsynth.rate)
     dev = torch.device("cuda:0")
-    batch = max(1, min(len(files) * args.starts, int(args.batch_size)))
-    voice = Voice(SynthConfig(batch_size=batch, sample_rate=rate, buffer_size_seconds=cfg.torchsynth.buffer_size_seconds,
-                              reproducible=cfg.torchsynth.reproducible)).to(dev)
-    T = voice.synthconfig.buffer_size
+    synth = dict(sample_rate=rate, buffer_size_seconds=cfg.torchsynth.buffer_size_seconds,
+                 reproducible=cfg.torchsynth.reproducible)
+    seg = None
     try:
-        if args.resample:
+        if args.split:                                   # the notes are the sounds: the Voice is built once S is known
+            seg, whole, in_rates, in_lengths = split_targets(files, rate, SynthConfig(batch_size=1, **synth).buffer_size,
+                                                             args, dev)
+        N = len(files) if seg is None else seg.audio.shape[0]
+        batch = max(1, min(N * args.starts, int(args.batch_size)))
+        voice = Voice(SynthConfig(batch_size=batch, **synth)).to(dev)
+        T = voice.synthconfig.buffer_size
+        if seg is not None:
+            target = seg.audio
+        elif args.resample:
             target, in_rates = resample_to(files, rate, T, dev)
         else:
             target = torch.from_numpy(np.stack([fit_length(read_wav(f, rate), T, f) for f in files])).to(dev)
@@ -221,7 +338,7 @@ def main(argv=None):
         sys.exit(f"match_audio.py: {e}")
     matcher = SoundMatcher(voice, loss=args.loss, mel_kwargs=dict(cfg.mel), lr=args.lr, betas=(args.beta1, args.beta2),
                            eps=args.eps)
-    N, nS = len(files), args.starts
+    nS = args.starts
     bank_idx = bank_dist = bank_voice = None
     if args.init == "random":
         init = torch.rand((N * nS, 78), generator=torch.Generator().manual_seed(args.seed)).to(dev)
@@ -293,19 +410,9 @@ def main(argv=None):
         del found
     res = matcher.fit(target, init_params01=init, steps=args.steps, return_audio=True)
     os.makedirs(args.out, exist_ok=True)
-    if args.resample:
-        from inverse_audio_synthesis_amd.resample import resample
-        audio = [None] * N
-        for sr in sorted(set(in_rates)):
-            idx = [i for i, r in enumerate(in_rates) if r == sr]
-            back = resample(res.audio[idx].contiguous(), rate, sr).cpu().numpy()
-            for k, i in enumerate(idx):
-                audio[i] = back[k]
-    else:
-        audio = res.audio.cpu().numpy()
-    for i, f in enumerate(files):
-        name = os.path.splitext(os.path.basename(f))[0]
-        rec = {"input": os.path.basename(f), "loss_kind": args.loss, "steps": args.steps,
+
+    def record(i, name):
+        rec = {"input": name, "loss_kind": args.loss, "steps": args.steps,
                "initial_loss": float(res.initial_loss[i]), "final_loss": float(res.loss[i]),
                "skipped": int(res.skipped[i]), "init": args.init, "params": params_record(res.params01[i])}
         if res.start is not None:
@@ -323,6 +430,24 @@ def main(argv=None):
             rec["voiced"] = bool(pitch.voiced[i])
             rec["estimated_midi"] = float(pitch.midi[i]) if rec["voiced"] else None
             rec["pitch_confidence"] = float(pitch.confidence[i])
+        return rec
+
+    if args.split:
+        write_notes(args, files, rate, seg, whole, in_rates, in_lengths, res.audio, record)
+        return
+    if args.resample:
+        from inverse_audio_synthesis_amd.resample import resample
+        audio = [None] * N
+        for sr in sorted(set(in_rates)):
+            idx = [i for i, r in enumerate(in_rates) if r == sr]
+            back = resample(res.audio[idx].contiguous(), rate, sr).cpu().numpy()
+            for k, i in enumerate(idx):
+                audio[i] = back[k]
+    else:
+        audio = res.audio.cpu().numpy()
+    for i, f in enumerate(files):
+        name = os.path.splitext(os.path.basename(f))[0]
+        rec = record(i, os.path.basename(f))
         if args.resample:
             rec["input_rate"], rec["synth_rate"] = int(in_rates[i]), rate
         with open(os.path.join(args.out, name + ".params.json"), "w") as fh:
