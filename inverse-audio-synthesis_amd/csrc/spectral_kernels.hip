@@ -30,9 +30,8 @@ static int stft_waves(int n_fft) {
   return 4;
 }
 
-// Complex numbers as 2-wide vectors: complex add/sub are one packed op and a complex multiply is pk_mul +
-// pk_fma (a packed fp32 op costs the SIMD 4 clocks, two plain ones 2 + 2: the same arithmetic time, fewer
-// instructions to issue).  8-byte aligned: LDS accesses are ds_*_b64.
+// Complex numbers as 2-wide vectors: complex add/sub are one packed op (a packed fp32 op costs the SIMD 4 clocks, two
+// plain ones 2 + 2: the same arithmetic time, fewer instructions to issue).  8-byte aligned: LDS accesses are ds_*_b64.
 typedef float cpx __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // floats of the re-packed mel weight table in LDS (every filter padded to a multiple of four taps), rounded to 16 bytes
@@ -42,15 +41,47 @@ __host__ __device__ static inline int mel_padded_words(int mel_nnz, int n_out) {
 __device__ __forceinline__ cpx cmk(float x, float y) { return (cpx){x, y}; }
 __device__ __forceinline__ cpx cadd(cpx a, cpx b) { return a + b; }
 __device__ __forceinline__ cpx csub(cpx a, cpx b) { return a - b; }
+// Operations with a swapped or negated operand -- a complex multiply, a multiplication by -i.  Written as 2-wide vector
+// expressions (the IAS_DIAG forms below, the superseded code) their operand (-a.y, a.y) or (a.y, -a.x) is BUILT first, a
+// v_xor_b32 for the sign and a v_mov_b32 for the pair (4 + 2 clocks) in front of every use: the compiler does not fold
+// the swap and the sign into the packed instruction's op_sel / neg modifiers (31 + 41 such instructions in the 343 of
+// the n_fft 1024 kernel's frame block).  So
+//   cmul        is written per component: a plain fp32 instruction takes its sign as a source modifier and either half
+//               of a pair as its operand, and four of them cost the SIMD what pk_mul + pk_fma do (4 x 2 = 2 x 4 clocks);
+//   a + (-i) x  and its kin are ONE v_pk_add_f32 whose modifiers carry the swap and the sign (inline asm: written per
+//               component the compiler re-packs them and pays for the sign with extra subtractions); a multiplication
+//               by -i is never materialised, the add that consumes it takes it.
+// Every product, every fused multiply-add and every rounding point is the vector form's -- the asm adds take sums,
+// never a product the compiler would have contracted into them -- so the results are the same bits
+// (tests/test_fft_forms_gpu.py: every kernel built on these helpers, product library against diagnostic library).
+#ifdef IAS_DIAG
 __device__ __forceinline__ cpx cmul(cpx a, cpx b) {
   return __builtin_elementwise_fma((cpx){-a.y, a.y}, (cpx){b.y, b.x}, (cpx){a.x, a.x} * b);
 }
 __device__ __forceinline__ cpx cmul_negi(cpx a) { return (cpx){a.y, -a.x}; }  // a * (-i)
+__device__ __forceinline__ cpx cadd_negi(cpx a, cpx x) { return a + cmul_negi(x); }   // a + (-i) x
+__device__ __forceinline__ cpx csub_negi(cpx a, cpx x) { return a - cmul_negi(x); }   // a - (-i) x
+__device__ __forceinline__ cpx cnegi_sub(cpx x, cpx a) { return cmul_negi(x) - a; }   // (-i) x - a
+#else
+__device__ __forceinline__ cpx cmul(cpx a, cpx b) {
+  return cmk(__builtin_fmaf(-a.y, b.y, a.x * b.x), __builtin_fmaf(a.y, b.x, a.x * b.y));
+}
+__device__ __forceinline__ cpx cadd_negi(cpx a, cpx x) {    // a + (-i) x = (a.x + x.y, a.y - x.x)
+  cpx r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(x)); return r;
+}
+__device__ __forceinline__ cpx csub_negi(cpx a, cpx x) {    // a - (-i) x = (a.x - x.y, a.y + x.x)
+  cpx r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(x)); return r;
+}
+__device__ __forceinline__ cpx cnegi_sub(cpx x, cpx a) {    // (-i) x - a = (x.y - a.x, -x.x - a.y)
+  cpx r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[1,1]" : "=v"(r) : "v"(x), "v"(a)); return r;
+}
+#endif
 
-// forward DFTs (kernel e^{-2 pi i nk/R}), in place, natural order
+// forward DFTs (kernel e^{-2 pi i nk/R}), in place, natural order.  A multiplication by -i is never materialised: the
+// add or subtract that consumes it takes the swap and the sign.
 __device__ __forceinline__ void dft4(cpx& v0, cpx& v1, cpx& v2, cpx& v3) {
-  const cpx t0 = cadd(v0, v2), t1 = csub(v0, v2), t2 = cadd(v1, v3), t3 = cmul_negi(csub(v1, v3));
-  v0 = cadd(t0, t2); v1 = cadd(t1, t3); v2 = csub(t0, t2); v3 = csub(t1, t3);
+  const cpx t0 = cadd(v0, v2), t1 = csub(v0, v2), t2 = cadd(v1, v3), t3 = csub(v1, v3);
+  v0 = cadd(t0, t2); v1 = cadd_negi(t1, t3); v2 = csub(t0, t2); v3 = csub_negi(t1, t3);
 }
 __device__ __forceinline__ void dft8(cpx* v) {
   cpx e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6];
@@ -58,12 +89,11 @@ __device__ __forceinline__ void dft8(cpx* v) {
   dft4(e0, e1, e2, e3);
   dft4(o0, o1, o2, o3);
   const float h = 0.70710678118654752f;
-  o1 = (o1 + cmul_negi(o1)) * h;                      // * W8^1 = (1 - i)/sqrt2
-  o2 = cmul_negi(o2);                                 // * W8^2 = -i
-  o3 = (cmul_negi(o3) - o3) * h;                      // * W8^3 = (-1 - i)/sqrt2
+  o1 = cadd_negi(o1, o1) * h;                         // * W8^1 = (1 - i)/sqrt2
+  o3 = cnegi_sub(o3, o3) * h;                         // * W8^3 = (-1 - i)/sqrt2
   v[0] = cadd(e0, o0); v[4] = csub(e0, o0);
   v[1] = cadd(e1, o1); v[5] = csub(e1, o1);
-  v[2] = cadd(e2, o2); v[6] = csub(e2, o2);
+  v[2] = cadd_negi(e2, o2); v[6] = csub_negi(e2, o2); // * W8^2 = -i
   v[3] = cadd(e3, o3); v[7] = csub(e3, o3);
 }
 __device__ __forceinline__ void dft16(cpx* v) {
