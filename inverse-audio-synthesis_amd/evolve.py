@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from . import voice_spec as S
-from .retrieval import EMPTY_INDEX, _bank_plan, l1_cdist, topk_merge
+from .retrieval import EMPTY_INDEX, Scorer, l1_cdist, topk_merge
 
 
 @dataclass
@@ -111,10 +111,8 @@ def evolve_search(voice, loss, target_audio=None, target_values=None, generation
     one ias_evolve_sample for the next generation.  The host reads nothing from the device inside the loop, every buffer
     is reused, no gradient is taken and ``voice.params01`` is left alone.  A run is a function of its arguments: the same
     seed gives the same bits."""
-    plan = _bank_plan(loss)
-    if (target_audio is None) == (target_values is None):
-        raise ValueError("give the target audio or its values")
-    B, T, P = voice.batch_size, voice.synthconfig.buffer_size, voice.params01.shape[1]
+    sc = Scorer(voice, loss)
+    B, T, K, P = sc.B, sc.T, sc.K, voice.params01.shape[1]
     dev = voice.params01.device
     G = int(generations)
     if G < 1:
@@ -132,15 +130,11 @@ def evolve_search(voice, loss, target_audio=None, target_values=None, generation
             raise ValueError(f"evolve_search: {name} must be finite and >= 0, got {v}")
     if float(sigma_max) < float(sigma_min) or not 0.0 <= float(alpha) <= 1.0:
         raise ValueError("evolve_search: need sigma_min <= sigma_max and alpha in [0, 1]")
-    F, n_out = plan.num_frames(T), plan.n_out
-    if target_values is None:
+    if target_audio is not None:
         if target_audio.dim() != 2 or target_audio.shape[1] != T:
             raise ValueError(f"target_audio must be [N, {T}] (the voice's buffer), got {tuple(target_audio.shape)}")
-        target_values = loss.target(target_audio.detach().to(device=dev, dtype=torch.float32))
-    if target_values.dim() != 3 or tuple(target_values.shape[1:]) != (F, n_out):
-        raise ValueError(f"target values must be [N, {F}, {n_out}], got {tuple(target_values.shape)}")
-    K = F * n_out
-    q = target_values.detach().to(torch.float32).contiguous().reshape(-1, K)
+        target_audio = target_audio.detach().to(device=dev, dtype=torch.float32)
+    q = sc.targets(target_audio, target_values, "evolve_search")
     N = q.shape[0]
     if N > 65535:
         raise ValueError(f"evolve_search: at most 65535 sounds per call (ias_topk_merge), got {N}")
@@ -156,11 +150,8 @@ def evolve_search(voice, loss, target_audio=None, target_values=None, generation
     nS = starts.shape[1]
     free = free_columns(frozen, dev)
 
-    lib = _lib.load()
-    nbytes = lib.ias_l1_cdist_workspace_bytes(1, M, K)
-    _lib.check(min(nbytes, 0), "ias_l1_cdist_workspace_bytes")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    values = torch.empty((M, F, n_out), dtype=torch.float32, device=dev)
+    ws = sc.workspace(1, M)
+    values = torch.empty((M, sc.F, sc.n_out), dtype=torch.float32, device=dev)
     block = torch.empty((N, M), dtype=torch.float32, device=dev)
     pop = torch.empty((N, M, P), dtype=torch.float32, device=dev)
     mean = starts[:, 0].contiguous().clone()
@@ -174,10 +165,10 @@ def evolve_search(voice, loss, target_audio=None, target_values=None, generation
 
     evolve_sample(mean, sigma, free, seed, 0, pop)
     pop[:, :nS] = starts
+    sounds = pop.unbind(0)                               # views, made once: pop is rewritten in place
     for g in range(G):
         for n in range(N):
-            for c in range(M // B):
-                values[c * B:(c + 1) * B] = loss.target(voice.render(pop[n, c * B:(c + 1) * B], normalize=True))
+            sc.fill(values, sounds[n])
             l1_cdist(q[n:n + 1], values.view(M, K), out=block[n:n + 1], workspace=ws)
         prev_idx.copy_(elite_idx)
         elite_params, prev_params = prev_params, elite_params

@@ -130,6 +130,40 @@ def _bank_plan(loss):
     raise ValueError(f"SpectralBank: the loss must be a MelSpectrogramL1 or an STFTL1, got {type(loss).__name__}")
 
 
+class Scorer:
+    """Render candidates and score them against targets under a per-sound L1 loss, for the resident bank, the streamed
+    search and ``evolve_search``: B rows of T samples per render, ``loss.target`` values [F, n_out] per row, K = F n_out."""
+
+    def __init__(self, voice, loss):
+        self.voice, self.loss, self.plan = voice, loss, _bank_plan(loss)
+        self.B, self.T = voice.batch_size, voice.synthconfig.buffer_size
+        self.F, self.n_out = self.plan.num_frames(self.T), self.plan.n_out
+        self.K = self.F * self.n_out
+
+    def targets(self, target_audio, target_values, what):
+        """The targets as audio [N, T] or as their ``loss.target`` values [N, F, n_out] -> q [N, K] fp32 contiguous."""
+        if (target_audio is None) == (target_values is None):
+            raise ValueError(f"{what}: give the target audio or its values")
+        if target_values is None:
+            target_values = self.loss.target(target_audio)
+        if tuple(target_values.shape[1:]) != (self.F, self.n_out):
+            raise ValueError(f"{what}: target values must be [N, {self.F}, {self.n_out}], got {tuple(target_values.shape)}")
+        return target_values.detach().to(torch.float32).contiguous().reshape(-1, self.K)
+
+    def workspace(self, N, M):
+        """The uint8 workspace of ``l1_cdist`` on [N, K] queries and [M, K] candidates."""
+        nbytes = _lib.load().ias_l1_cdist_workspace_bytes(N, M, self.K)
+        _lib.check(min(nbytes, 0), "ias_l1_cdist_workspace_bytes")
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.voice.params01.device)
+
+    def fill(self, values, params, row=0):
+        """values[row:row + len(params)] = ``loss.target`` of the renders of params [j B, 78], row m at Voice row m % B."""
+        B = self.B
+        for j in range(params.shape[0] // B):
+            values[row + j * B:row + (j + 1) * B] = self.loss.target(      # (unnamed: the next render reuses its buffer)
+                self.voice.render(params[j * B:(j + 1) * B], normalize=True))
+
+
 class SpectralBank:
     """A bank of rendered voices and their spectral values under a per-sound L1 loss (``MelSpectrogramL1`` or ``STFTL1``,
     e.g. ``SoundMatcher.loss``), searched with the loss itself: ``distances(target_values)[n, m]`` is the quantity
@@ -143,47 +177,36 @@ class SpectralBank:
 
     def __init__(self, voice, loss, batch_indices):
         from .voice import sample_params01
-        self.plan = _bank_plan(loss)
-        self.loss = loss
-        B, T = voice.batch_size, voice.synthconfig.buffer_size
-        dev = voice.params01.device
+        sc = self._scorer = Scorer(voice, loss)
+        self.plan, self.loss = sc.plan, loss
+        B, dev = sc.B, voice.params01.device
         idx = [int(i) for i in batch_indices]
         if not idx:
             raise ValueError("SpectralBank: no batch indices")
-        F, n_out = self.plan.num_frames(T), self.plan.n_out
         self.params01 = torch.empty((len(idx) * B, voice.params01.shape[1]), dtype=torch.float32, device=dev)
-        self.values = torch.empty((len(idx) * B, F, n_out), dtype=torch.float32, device=dev)
+        self.values = torch.empty((len(idx) * B, sc.F, sc.n_out), dtype=torch.float32, device=dev)
         with torch.no_grad():
             for j, i in enumerate(idx):
                 p = sample_params01(B, i).to(dev)
                 self.params01[j * B:(j + 1) * B] = p
-                self.values[j * B:(j + 1) * B] = loss.target(voice.render(p, normalize=True))
+                sc.fill(self.values, p, j * B)
 
     @staticmethod
     def nbytes(voice, loss, n_batches):
         """Bytes of the values of a bank of ``n_batches`` voice batches (before building it)."""
-        plan = _bank_plan(loss)
-        return 4 * int(n_batches) * voice.batch_size * plan.num_frames(voice.synthconfig.buffer_size) * plan.n_out
+        sc = Scorer(voice, loss)
+        return 4 * int(n_batches) * sc.B * sc.K
 
     @torch.no_grad()
     def distances(self, target_values):
         """target_values [N, F, n_out] (``loss.target`` of the targets) -> [N, M] fp32 mean |target - bank| per pair."""
-        if tuple(target_values.shape[1:]) != tuple(self.values.shape[1:]):
-            raise ValueError(f"target values must be [N, {self.values.shape[1]}, {self.values.shape[2]}], got "
-                             f"{tuple(target_values.shape)}")
-        K = self.values[0].numel()
-        q = target_values.detach().to(torch.float32).contiguous().reshape(-1, K)
-        return l1_cdist(q, self.values.reshape(-1, K))
+        return l1_cdist(self._scorer.targets(None, target_values, "SpectralBank"), self.values.flatten(1))
 
     @torch.no_grad()
     def nearest(self, target_audio=None, target_values=None, k=1):
         """The k nearest bank voices of each target (give the audio [N, T] or its ``loss.target`` values) -> (dist [N, k]
         fp32, idx [N, k] int64) in ``rank_distances`` order; ``params01[idx]`` are the starts for ``SoundMatcher.fit``."""
-        if (target_audio is None) == (target_values is None):
-            raise ValueError("give the target audio or its values")
-        if target_values is None:
-            target_values = self.loss.target(target_audio)
-        d = self.distances(target_values)
+        d = l1_cdist(self._scorer.targets(target_audio, target_values, "SpectralBank"), self.values.flatten(1))
         k = min(int(k), d.shape[1])
         idx = rank_distances(d)[:, :k]
         return torch.gather(d, 1, idx), idx
@@ -201,9 +224,7 @@ class SpectralBank:
         convention as for the resident bank: item m = j B + r is row r of ``batch_indices[j]``, rendered at row r.
         ``params01`` is drawn again on the host for the winning batches only; ``voice.params01`` is left alone."""
         from .voice import sample_params01
-        plan = _bank_plan(loss)
-        if (target_audio is None) == (target_values is None):
-            raise ValueError("give the target audio or its values")
+        sc = Scorer(voice, loss)
         idx = [int(i) for i in batch_indices]
         if not idx:
             raise ValueError("SpectralBank: no batch indices")
@@ -211,26 +232,17 @@ class SpectralBank:
         if C < 1:
             raise ValueError("SpectralBank.search: chunk_batches must be >= 1")
         C = min(C, len(idx))
-        B, T, P = voice.batch_size, voice.synthconfig.buffer_size, voice.params01.shape[1]
+        B, K, P = sc.B, sc.K, voice.params01.shape[1]
         dev = voice.params01.device
-        F, n_out = plan.num_frames(T), plan.n_out
-        if target_values is None:
-            target_values = loss.target(target_audio)
-        if tuple(target_values.shape[1:]) != (F, n_out):
-            raise ValueError(f"target values must be [N, {F}, {n_out}], got {tuple(target_values.shape)}")
-        K = F * n_out
-        q = target_values.detach().to(torch.float32).contiguous().reshape(-1, K)
+        q = sc.targets(target_audio, target_values, "SpectralBank.search")
         N = q.shape[0]
         k = min(int(k), len(idx) * B)
         if not 1 <= k <= 64:
             raise ValueError(f"SpectralBank.search: k must be in 1..64 (ias_topk_merge), got {k}")
 
-        lib = _lib.load()
-        nbytes = lib.ias_l1_cdist_workspace_bytes(N, C * B, K)
-        _lib.check(min(nbytes, 0), "ias_l1_cdist_workspace_bytes")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = sc.workspace(N, C * B)
         block = torch.empty(N * C * B, dtype=torch.float32, device=dev)
-        values = torch.empty((C * B, F, n_out), dtype=torch.float32, device=dev)
+        values = torch.empty((C * B, sc.F, sc.n_out), dtype=torch.float32, device=dev)
         params = torch.empty((C * B, P), dtype=torch.float32, device=dev)
         # two pinned staging buffers: the host fills one while the other's upload may still be queued behind the
         # previous chunk's kernels; an event per buffer says when its upload has been consumed
@@ -248,8 +260,7 @@ class SpectralBank:
                 host[j * B:(j + 1) * B] = sample_params01(B, i)
             params[:n * B].copy_(host[:n * B], non_blocking=True)
             uploaded[c & 1].record()
-            for j in range(n):
-                values[j * B:(j + 1) * B] = loss.target(voice.render(params[j * B:(j + 1) * B], normalize=True))
+            sc.fill(values, params[:n * B])
             d = l1_cdist(q, values[:n * B].reshape(n * B, K), out=block[:N * n * B].view(N, n * B), workspace=ws)
             topk_merge(d, j0 * B, best_dist, best_idx)
 

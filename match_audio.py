@@ -42,6 +42,7 @@ import os
 import sys
 import wave
 import warnings
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -49,11 +50,19 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 
-def read_wav_any_rate(path):
+def _refuse_rate(path, sr, rate, remedy):
+    if sr != rate:
+        raise ValueError(f"{path}: sample rate {sr} Hz, the synth runs at {rate} Hz (torchsynth.rate); {remedy} "
+                         f"torchsynth.rate={sr}")
+
+
+def read_wav_any_rate(path, rate=None):
     """-> (mono float32 samples in [-1, 1), the file's rate).  16-, 24- or 32-bit little-endian signed integer PCM,
-    channels averaged; other widths are refused (ValueError)."""
+    channels averaged; other widths, and with ``rate`` given any other rate, are refused (ValueError)."""
     with wave.open(path, "rb") as w:
         nch, width, sr, nframes = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
+        if rate is not None:
+            _refuse_rate(path, sr, rate, "resample the file or pass")
         raw = w.readframes(nframes)
     if width == 2:
         x = np.frombuffer(raw, dtype="<i2").astype(np.float64) / 32768.0
@@ -71,35 +80,7 @@ def read_wav_any_rate(path):
 def read_wav(path, rate):
     """-> mono float32 samples in [-1, 1).  16-, 24- or 32-bit integer PCM, channels averaged; any rate but ``rate`` is
     refused (ValueError)."""
-    with wave.open(path, "rb") as w:
-        sr = w.getframerate()
-    if sr != rate:
-        raise ValueError(f"{path}: sample rate {sr} Hz, the synth runs at {rate} Hz (torchsynth.rate); resample the file "
-                         f"or pass torchsynth.rate={sr}")
-    return read_wav_any_rate(path)[0]
-
-
-def resample_to(files, rate, length, dev):
-    """--resample: read every file at its own rate and bring it to ``rate`` on the device, one ``resample`` call per
-    distinct input rate (the files of a rate zero-padded to the longest; a row's output does not depend on the others),
-    then crop or pad to ``length`` synth-rate samples.  -> ([N, length] device fp32, [N] input rates)."""
-    import torch
-    from inverse_audio_synthesis_amd.resample import resample, resample_plan, output_length
-    read = [read_wav_any_rate(f) for f in files]
-    rates = [sr for _x, sr in read]
-    out = [None] * len(files)
-    for sr in sorted(set(rates)):
-        idx = [i for i, r in enumerate(rates) if r == sr]
-        L = max(len(read[i][0]) for i in idx)
-        x = np.zeros((len(idx), L), dtype=np.float32)
-        for k, i in enumerate(idx):
-            x[k, :len(read[i][0])] = read[i][0]
-        y = resample(torch.from_numpy(x).to(dev), sr, rate)
-        o, n, _w, _K = resample_plan(sr, rate)
-        for k, i in enumerate(idx):
-            yi = y[k, :output_length(len(read[i][0]), o, n)].cpu().numpy()
-            out[i] = fit_length(yi, length, f"{files[i]} (resampled {sr} -> {rate} Hz)")
-    return torch.from_numpy(np.stack(out)).to(dev), rates
+    return read_wav_any_rate(path, rate)[0]
 
 
 def write_wav(path, samples, rate):
@@ -114,14 +95,31 @@ def write_wav(path, samples, rate):
 
 
 def fit_length(x, length, name="input"):
-    """Crop or zero-pad to ``length`` samples, with a warning when the length changes."""
-    if len(x) > length:
-        warnings.warn(f"{name}: {len(x)} samples, cropped to the synth buffer of {length}")
-        return x[:length]
-    if len(x) < length:
-        warnings.warn(f"{name}: {len(x)} samples, zero-padded to the synth buffer of {length}")
-        return np.concatenate([x, np.zeros(length - len(x), dtype=x.dtype)])
-    return x
+    """Crop or zero-pad to ``length`` samples, with a warning when the length changes (``name=None``: silently)."""
+    if len(x) == length:
+        return x
+    if name is not None:
+        change = "cropped" if len(x) > length else "zero-padded"
+        warnings.warn(f"{name}: {len(x)} samples, {change} to the synth buffer of {length}")
+    return x[:length] if len(x) > length else np.concatenate([x, np.zeros(length - len(x), dtype=x.dtype)])
+
+
+def resample_rows(rows, from_rates, to_rates, dev):
+    """1-D float32 arrays or tensors, row i at ``from_rates[i]`` -> 1-D device tensors, row i at ``to_rates[i]`` and of
+    ``output_length`` of its own length: one ``resample`` call per distinct pair of rates, in ascending order, its rows
+    zero-padded to the longest of them (a row's output does not depend on the others)."""
+    import torch
+    from inverse_audio_synthesis_amd.resample import resample, resample_plan, output_length
+    rows = [torch.as_tensor(r) for r in rows]
+    pairs = list(zip(from_rates, to_rates))
+    out = [None] * len(rows)
+    for a, b in sorted(set(pairs)):
+        idx = [i for i, ab in enumerate(pairs) if ab == (a, b)]
+        y = resample(torch.nn.utils.rnn.pad_sequence([rows[i] for i in idx], batch_first=True).to(dev), a, b)
+        o, n, _w, _K = resample_plan(a, b)
+        for k, i in enumerate(idx):
+            out[i] = y[k, :output_length(len(rows[i]), o, n)]
+    return out
 
 
 def params_record(params01_row):
@@ -134,37 +132,30 @@ def params_record(params01_row):
             for i, (m, n, *_r) in enumerate(S.PARAMS)]
 
 
-def split_targets(files, rate, T, args, dev):
-    """--split: read every file whole (with --resample at its own rate, brought to ``rate`` on the device), zero-pad to the
-    longest, find the onsets and cut one buffer of ``T`` samples per note.  -> (``onset.NoteSegments`` with S notes, the
-    padded recordings [N, L] at ``rate``, the files' rates, their lengths in samples at their own rates)."""
+@dataclass
+class Targets:
+    audio: object                   # [N, T] device fp32 at the synth's rate: the sounds to match (files, or notes)
+    in_rates: list                  # per file: its own rate
+    in_lengths: list                # per file: its length in samples at its own rate
+    seg: object = None              # --split: the ``onset.NoteSegments`` of the N notes
+    whole: object = None            # --split: the recordings [files, L] at the synth's rate, zero-padded to the longest
+
+
+@dataclass
+class Provenance:
+    """Where the kept start of every sound came from, for its record."""
+    bank: object = None             # (dist, idx) [N, starts] device tensors: the nearest bank voices, or None
+    evolve: object = None           # (dist, idx) [N, starts]: the best elites of the evolutionary search, or None
+    pitch: object = None            # ``pitch.PitchResult`` of the N sounds, or None
+
+
+def split_targets(rows, files, rate, T, args):
+    """--split: zero-pad the recordings (1-D device tensors at ``rate``) to the longest, find the onsets and cut one buffer
+    of ``T`` samples per note -> (``onset.NoteSegments`` with S notes, the padded recordings [files, L])."""
     import torch
     from inverse_audio_synthesis_amd.onset import detect_onsets, split_notes
-    read = [read_wav_any_rate(f) for f in files]
-    in_rates = [sr for _x, sr in read]
-    in_lengths = [len(x) for x, _sr in read]
-    rows = [None] * len(files)
-    if args.resample:
-        from inverse_audio_synthesis_amd.resample import resample, resample_plan, output_length
-        for sr in sorted(set(in_rates)):
-            idx = [i for i, r in enumerate(in_rates) if r == sr]
-            x = np.zeros((len(idx), max(in_lengths[i] for i in idx)), dtype=np.float32)
-            for k, i in enumerate(idx):
-                x[k, :in_lengths[i]] = read[i][0]
-            y = resample(torch.from_numpy(x).to(dev), sr, rate)
-            o, n, _w, _K = resample_plan(sr, rate)
-            for k, i in enumerate(idx):
-                rows[i] = y[k, :output_length(in_lengths[i], o, n)]
-    else:
-        for i, (x, sr) in enumerate(read):
-            if sr != rate:
-                raise ValueError(f"{files[i]}: sample rate {sr} Hz, the synth runs at {rate} Hz (torchsynth.rate); pass "
-                                 f"--resample or torchsynth.rate={sr}")
-            rows[i] = torch.from_numpy(x).to(dev)
-    lengths = torch.tensor([int(r.numel()) for r in rows], dtype=torch.int64, device=dev)
-    whole = torch.zeros((len(rows), max(int(r.numel()) for r in rows)), dtype=torch.float32, device=dev)
-    for i, r in enumerate(rows):
-        whole[i, :r.numel()] = r
+    lengths = torch.tensor([int(r.numel()) for r in rows], dtype=torch.int64, device=rows[0].device)
+    whole = torch.nn.utils.rnn.pad_sequence(rows, batch_first=True)
     try:
         onsets = detect_onsets(whole, rate, delta=args.onset_delta, max_onsets=args.max_notes)
     except RuntimeError as e:
@@ -174,51 +165,32 @@ def split_targets(files, rate, T, args, dev):
             warnings.warn(f"{f}: {c} onsets, the first {args.max_notes} are kept (--max-notes)")
     seg = split_notes(whole, lengths, onsets, T, int(round(args.fade_ms * 1e-3 * rate)))
     print(f"match_audio.py: {seg.audio.shape[0]} notes in {len(files)} files", flush=True)
-    return seg, whole, in_rates, in_lengths
+    return seg, whole
 
 
-def write_notes(args, files, rate, seg, whole, in_rates, in_lengths, renders, record):
-    """--split: NAME.notes.json and the full-length NAME.match.wav of every input."""
-    from inverse_audio_synthesis_amd.onset import join_notes, note_gains
-    gain = note_gains(seg.audio, renders, seg.length)
-    joined = join_notes(renders.contiguous(), seg, whole.shape[0], whole.shape[1], gain)
-    rows, starts, lengths = seg.row.tolist(), seg.start.tolist(), seg.length.tolist()
-    gains, strengths = gain.tolist(), seg.strength.tolist()
-    audio = [None] * len(files)
+def load_targets(args, files, rate, T, dev):
+    """Read the files, with --resample at any rate and brought to ``rate`` on the device -> ``Targets``: one buffer of ``T``
+    samples per file, cropped or zero-padded with a warning, or with --split one per note of the files read whole."""
+    import torch
+    plain = not (args.resample or args.split)            # then a file is refused or fitted as soon as it is read
+    rows, in_rates, in_lengths = [], [], []
+    for f in files:
+        x, sr = read_wav_any_rate(f, rate if plain else None)
+        rows.append(fit_length(x, T, f) if plain else x)
+        in_rates.append(sr)
+        in_lengths.append(len(x))
     if args.resample:
-        from inverse_audio_synthesis_amd.resample import resample
-        for sr in sorted(set(in_rates)):
-            idx = [i for i, r in enumerate(in_rates) if r == sr]
-            back = resample(joined[idx].contiguous(), rate, sr).cpu().numpy()
-            for k, i in enumerate(idx):
-                audio[i] = fit_to(back[k], in_lengths[i])
-    else:
-        host = joined.cpu().numpy()
-        for i in range(len(files)):
-            audio[i] = host[i, :in_lengths[i]]
-    for i, f in enumerate(files):
-        name = os.path.splitext(os.path.basename(f))[0]
-        notes = []
-        for s in [s for s, r in enumerate(rows) if r == i]:
-            note = {"onset_sample": starts[s], "onset_seconds": starts[s] / rate, "length_samples": lengths[s],
-                    "strength": strengths[s], "gain": gains[s]}
-            note.update(record(s, os.path.basename(f)))
-            notes.append(note)
-        doc = {"input": os.path.basename(f), "rate": rate, "notes": notes}
-        if args.resample:
-            doc["input_rate"] = int(in_rates[i])
-        with open(os.path.join(args.out, name + ".notes.json"), "w") as fh:
-            json.dump(doc, fh, indent=1)
-        write_wav(os.path.join(args.out, name + ".match.wav"), audio[i], in_rates[i] if args.resample else rate)
-        print(json.dumps({"input": doc["input"], "notes": len(notes),
-                          "final_loss": [n["final_loss"] for n in notes]}), flush=True)
-
-
-def fit_to(x, length):
-    """Crop or zero-pad to ``length`` samples, silently (a resampled-back recording against the input's length)."""
-    if len(x) >= length:
-        return x[:length]
-    return np.concatenate([x, np.zeros(length - len(x), dtype=x.dtype)])
+        rows = resample_rows(rows, in_rates, [rate] * len(files), dev)
+        if not args.split:                               # the warnings come rate by rate, as the resampling goes
+            for i in sorted(range(len(files)), key=lambda i: in_rates[i]):
+                rows[i] = fit_length(rows[i].cpu().numpy(), T, f"{files[i]} (resampled {in_rates[i]} -> {rate} Hz)")
+    elif args.split:
+        for f, sr in zip(files, in_rates):
+            _refuse_rate(f, sr, rate, "pass --resample or")
+    if args.split:
+        seg, whole = split_targets([torch.as_tensor(r).to(dev) for r in rows], files, rate, T, args)
+        return Targets(seg.audio, in_rates, in_lengths, seg, whole)
+    return Targets(torch.from_numpy(np.stack(rows)).to(dev), in_rates, in_lengths)
 
 
 INITS = ("center", "random", "bank")
@@ -307,6 +279,144 @@ def parse_args(argv=None):
     return args, files, overrides
 
 
+def search_stage(cfg, matcher, args, rate, dev):
+    """-> (voice, loss) of --init bank and --evolve: a Voice of ``BANK_BATCH`` rows and the matcher's loss, or a mel loss
+    (the ``mel.*`` settings) where that is multi_resolution_stft, which is not the L1 of one array."""
+    from inverse_audio_synthesis_amd.spectral import MelSpectrogramL1
+    from inverse_audio_synthesis_amd.voice import SynthConfig, Voice
+    voice = Voice(SynthConfig(batch_size=BANK_BATCH, sample_rate=rate,
+                              buffer_size_seconds=cfg.torchsynth.buffer_size_seconds,
+                              reproducible=cfg.torchsynth.reproducible)).to(dev)
+    if args.loss != "multi_resolution_stft":
+        return voice, matcher.loss
+    kw = dict(cfg.mel)
+    kw.setdefault("sample_rate", rate)
+    return voice, MelSpectrogramL1(**kw).to(dev)
+
+
+def initial_starts(args, stage, target, prov):
+    """--init -> the starts [N, 78] or [N, S, 78] (None: the centre); --init bank names its voices in ``prov``."""
+    import torch
+    N, nS = target.shape[0], args.starts
+    if args.init == "random":
+        init = torch.rand((N * nS, 78), generator=torch.Generator().manual_seed(args.seed)).to(target.device)
+        return init.reshape(N, nS, 78) if nS > 1 else init
+    if args.init != "bank":
+        return None
+    from inverse_audio_synthesis_amd.retrieval import SpectralBank
+    voice, loss = stage
+    if args.bank_stream is not None:
+        chunk = min(args.bank_stream, args.bank_batches)
+        nbytes = SpectralBank.nbytes(voice, loss, chunk)
+        print(f"match_audio.py: searching a spectral bank of {args.bank_batches * BANK_BATCH} voices in chunks of "
+              f"{chunk * BANK_BATCH} ({nbytes} bytes)", flush=True)
+        dist, idx, init = SpectralBank.search(voice, loss, range(args.bank_batches), target_audio=target, k=nS,
+                                              chunk_batches=chunk)
+        prov.bank = (dist, idx)
+        return init
+    nbytes = SpectralBank.nbytes(voice, loss, args.bank_batches)
+    print(f"match_audio.py: building a spectral bank of {args.bank_batches * BANK_BATCH} voices ({nbytes} bytes)",
+          flush=True)
+    bank = SpectralBank(voice, loss, range(args.bank_batches))
+    prov.bank = bank.nearest(target_audio=target, k=nS)
+    return bank.params01[prov.bank[1].reshape(-1)].reshape(N, -1, 78)
+
+
+def pitch_stage(args, target, rate, init, prov):
+    """--pitch: estimate every target's note (``prov.pitch``) and move ``keyboard.midi_f0`` of its starts onto it."""
+    import torch
+    from inverse_audio_synthesis_amd.pitch import estimate_pitch, retune
+    try:
+        prov.pitch = estimate_pitch(target, rate, midi_lo=args.pitch_lo, midi_hi=args.pitch_hi)
+    except ValueError as e:
+        sys.exit(f"match_audio.py: --pitch: {e}")
+    if init is None:                                     # --init center: the centre matrix, so that it can be retuned
+        init = torch.full((target.shape[0], 78), 0.5, dtype=torch.float32, device=target.device)
+    return retune(init, prov.pitch)
+
+
+def evolve_stage(args, stage, target, init, prov):
+    """--evolve: the search from ``init`` -> its --starts best elites as the starts; ``prov`` names them."""
+    from inverse_audio_synthesis_amd.evolve import evolve_search
+    print(f"match_audio.py: evolutionary search, {args.evolve} generations of {args.evolve_population} candidates per "
+          f"sound, {args.evolve_elites} elites", flush=True)
+    found = evolve_search(*stage, target_audio=target, generations=args.evolve, population=args.evolve_population,
+                          elites=args.evolve_elites, init_params01=init, sigma0=args.evolve_sigma, seed=args.seed)
+    nS = args.starts
+    prov.evolve, prov.bank = (found.dist[:, :nS], found.idx[:, :nS]), None   # the kept start is no longer a bank voice
+    return found.params01[:, :nS].contiguous() if nS > 1 else found.params01[:, 0].contiguous()
+
+
+def record(args, res, prov, i, name):
+    """The fields of sound i's params.json record."""
+    rec = {"input": name, "loss_kind": args.loss, "steps": args.steps,
+           "initial_loss": float(res.initial_loss[i]), "final_loss": float(res.loss[i]),
+           "skipped": int(res.skipped[i]), "init": args.init, "params": params_record(res.params01[i])}
+    s = 0
+    if res.start is not None:
+        s = rec["start"] = int(res.start[i])
+    if prov.bank is not None:
+        rec["bank_index"], rec["bank_distance"] = int(prov.bank[1][i, s]), float(prov.bank[0][i, s])
+    if prov.evolve is not None:
+        rec["evolve_generations"], rec["evolve_population"] = args.evolve, args.evolve_population
+        rec["evolve_index"], rec["evolve_distance"] = int(prov.evolve[1][i, s]), float(prov.evolve[0][i, s])
+    if prov.pitch is not None:
+        rec["voiced"] = bool(prov.pitch.voiced[i])
+        rec["estimated_midi"] = float(prov.pitch.midi[i]) if rec["voiced"] else None
+        rec["pitch_confidence"] = float(prov.pitch.confidence[i])
+    return rec
+
+
+def file_docs(args, files, rate, tg, res, prov):
+    """-> (the best renders [files, T], NAME.params.json's content per file, its stdout line per file)."""
+    docs = [record(args, res, prov, i, os.path.basename(f)) for i, f in enumerate(files)]
+    if args.resample:
+        for doc, sr in zip(docs, tg.in_rates):
+            doc["input_rate"], doc["synth_rate"] = int(sr), rate
+    return res.audio, docs, [{key: doc[key] for key in ("input", "initial_loss", "final_loss")} for doc in docs]
+
+
+def notes_docs(args, files, rate, tg, res, prov):
+    """--split -> (the recordings [files, L] put together from the best renders, NAME.notes.json's content per file, its
+    stdout line per file)."""
+    from inverse_audio_synthesis_amd.onset import join_notes, note_gains
+    seg = tg.seg
+    gain = note_gains(seg.audio, res.audio, seg.length)
+    joined = join_notes(res.audio.contiguous(), seg, tg.whole.shape[0], tg.whole.shape[1], gain)
+    rows, starts, lengths = seg.row.tolist(), seg.start.tolist(), seg.length.tolist()
+    gains, strengths = gain.tolist(), seg.strength.tolist()
+    docs = []
+    for i, f in enumerate(files):
+        notes = []
+        for s in [s for s, r in enumerate(rows) if r == i]:
+            note = {"onset_sample": starts[s], "onset_seconds": starts[s] / rate, "length_samples": lengths[s],
+                    "strength": strengths[s], "gain": gains[s]}
+            note.update(record(args, res, prov, s, os.path.basename(f)))
+            notes.append(note)
+        docs.append({"input": os.path.basename(f), "rate": rate, "notes": notes})
+        if args.resample:
+            docs[i]["input_rate"] = int(tg.in_rates[i])
+    lines = [{"input": doc["input"], "notes": len(doc["notes"]), "final_loss": [n["final_loss"] for n in doc["notes"]]}
+             for doc in docs]
+    return joined, docs, lines
+
+
+def write_outputs(args, files, rate, tg, audio, docs, lines):
+    """Per input NAME: ``docs[i]`` as NAME.notes.json (--split) or NAME.params.json, row i of audio [files, L] (on the
+    device, at ``rate``) as NAME.match.wav, with --resample at the file's own rate, and ``lines[i]`` to stdout."""
+    if args.resample:
+        host = [y.cpu().numpy() for y in resample_rows(list(audio), [rate] * len(files), tg.in_rates, audio.device)]
+    else:
+        host = audio.cpu().numpy()
+    for i, f in enumerate(files):
+        name = os.path.splitext(os.path.basename(f))[0]
+        with open(os.path.join(args.out, name + (".notes.json" if args.split else ".params.json")), "w") as fh:
+            json.dump(docs[i], fh, indent=1)
+        x = fit_length(host[i], tg.in_lengths[i], None) if args.split else host[i]
+        write_wav(os.path.join(args.out, name + ".match.wav"), x, tg.in_rates[i])
+        print(json.dumps(lines[i]), flush=True)
+
+
 def main(argv=None):
     args, files, overrides = parse_args(argv)
 
@@ -319,142 +429,26 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     synth = dict(sample_rate=rate, buffer_size_seconds=cfg.torchsynth.buffer_size_seconds,
                  reproducible=cfg.torchsynth.reproducible)
-    seg = None
     try:
-        if args.split:                                   # the notes are the sounds: the Voice is built once S is known
-            seg, whole, in_rates, in_lengths = split_targets(files, rate, SynthConfig(batch_size=1, **synth).buffer_size,
-                                                             args, dev)
-        N = len(files) if seg is None else seg.audio.shape[0]
-        batch = max(1, min(N * args.starts, int(args.batch_size)))
-        voice = Voice(SynthConfig(batch_size=batch, **synth)).to(dev)
-        T = voice.synthconfig.buffer_size
-        if seg is not None:
-            target = seg.audio
-        elif args.resample:
-            target, in_rates = resample_to(files, rate, T, dev)
-        else:
-            target = torch.from_numpy(np.stack([fit_length(read_wav(f, rate), T, f) for f in files])).to(dev)
+        tg = load_targets(args, files, rate, SynthConfig(batch_size=1, **synth).buffer_size, dev)
+        N = tg.audio.shape[0]                            # with --split the notes are the sounds: the Voice is built now
+        voice = Voice(SynthConfig(batch_size=max(1, min(N * args.starts, int(args.batch_size))), **synth)).to(dev)
     except ValueError as e:
         sys.exit(f"match_audio.py: {e}")
     matcher = SoundMatcher(voice, loss=args.loss, mel_kwargs=dict(cfg.mel), lr=args.lr, betas=(args.beta1, args.beta2),
                            eps=args.eps)
-    nS = args.starts
-    bank_idx = bank_dist = bank_voice = None
-    if args.init == "random":
-        init = torch.rand((N * nS, 78), generator=torch.Generator().manual_seed(args.seed)).to(dev)
-        init = init.reshape(N, nS, 78) if nS > 1 else init
-    elif args.init == "bank":
-        from inverse_audio_synthesis_amd.retrieval import SpectralBank
-        from inverse_audio_synthesis_amd.spectral import MelSpectrogramL1
-        bank_voice = Voice(SynthConfig(batch_size=BANK_BATCH, sample_rate=rate,
-                                       buffer_size_seconds=cfg.torchsynth.buffer_size_seconds,
-                                       reproducible=cfg.torchsynth.reproducible)).to(dev)
-        if args.loss == "multi_resolution_stft":
-            kw = dict(cfg.mel)
-            kw.setdefault("sample_rate", rate)
-            bank_loss = MelSpectrogramL1(**kw).to(dev)
-        else:
-            bank_loss = matcher.loss
-        if args.bank_stream is not None:
-            chunk = min(args.bank_stream, args.bank_batches)
-            nbytes = SpectralBank.nbytes(bank_voice, bank_loss, chunk)
-            print(f"match_audio.py: searching a spectral bank of {args.bank_batches * BANK_BATCH} voices in chunks of "
-                  f"{chunk * BANK_BATCH} ({nbytes} bytes)", flush=True)
-            bank_dist, bank_idx, init = SpectralBank.search(bank_voice, bank_loss, range(args.bank_batches),
-                                                            target_audio=target, k=nS, chunk_batches=chunk)
-            nS = bank_idx.shape[1]
-        else:
-            nbytes = SpectralBank.nbytes(bank_voice, bank_loss, args.bank_batches)
-            print(f"match_audio.py: building a spectral bank of {args.bank_batches * BANK_BATCH} voices "
-                  f"({nbytes} bytes)", flush=True)
-            bank = SpectralBank(bank_voice, bank_loss, range(args.bank_batches))
-            bank_dist, bank_idx = bank.nearest(target_audio=target, k=nS)
-            nS = bank_idx.shape[1]
-            init = bank.params01[bank_idx.reshape(-1)].reshape(N, nS, 78)
-            del bank
-    else:
-        init = None
-    pitch = None
+    stage = search_stage(cfg, matcher, args, rate, dev) if args.init == "bank" or args.evolve > 0 else None
+    prov = Provenance()
+    init = initial_starts(args, stage, tg.audio, prov)
     if args.pitch:
-        from inverse_audio_synthesis_amd.pitch import estimate_pitch, retune
-        try:
-            pitch = estimate_pitch(target, rate, midi_lo=args.pitch_lo, midi_hi=args.pitch_hi)
-        except ValueError as e:
-            sys.exit(f"match_audio.py: --pitch: {e}")
-        if init is None:                                 # --init center: the centre matrix, so that it can be retuned
-            init = torch.full((N, 78), 0.5, dtype=torch.float32, device=dev)
-        init = retune(init, pitch)
-    evolve_idx = evolve_dist = None
+        init = pitch_stage(args, tg.audio, rate, init, prov)
     if args.evolve > 0:
-        from inverse_audio_synthesis_amd.evolve import evolve_search
-        if bank_voice is None:
-            bank_voice = Voice(SynthConfig(batch_size=BANK_BATCH, sample_rate=rate,
-                                           buffer_size_seconds=cfg.torchsynth.buffer_size_seconds,
-                                           reproducible=cfg.torchsynth.reproducible)).to(dev)
-            if args.loss == "multi_resolution_stft":
-                from inverse_audio_synthesis_amd.spectral import MelSpectrogramL1
-                kw = dict(cfg.mel)
-                kw.setdefault("sample_rate", rate)
-                bank_loss = MelSpectrogramL1(**kw).to(dev)
-            else:
-                bank_loss = matcher.loss
-        print(f"match_audio.py: evolutionary search, {args.evolve} generations of {args.evolve_population} candidates per "
-              f"sound, {args.evolve_elites} elites", flush=True)
-        found = evolve_search(bank_voice, bank_loss, target_audio=target, generations=args.evolve,
-                              population=args.evolve_population, elites=args.evolve_elites, init_params01=init,
-                              sigma0=args.evolve_sigma, seed=args.seed)
-        nS = args.starts
-        evolve_idx, evolve_dist = found.idx[:, :nS], found.dist[:, :nS]
-        init = found.params01[:, :nS].contiguous() if nS > 1 else found.params01[:, 0].contiguous()
-        bank_idx = bank_dist = None                      # the kept start is an elite, no longer a bank voice
-        del found
-    res = matcher.fit(target, init_params01=init, steps=args.steps, return_audio=True)
+        init = evolve_stage(args, stage, tg.audio, init, prov)
+    res = matcher.fit(tg.audio, init_params01=init, steps=args.steps, return_audio=True)
     os.makedirs(args.out, exist_ok=True)
-
-    def record(i, name):
-        rec = {"input": name, "loss_kind": args.loss, "steps": args.steps,
-               "initial_loss": float(res.initial_loss[i]), "final_loss": float(res.loss[i]),
-               "skipped": int(res.skipped[i]), "init": args.init, "params": params_record(res.params01[i])}
-        if res.start is not None:
-            rec["start"] = int(res.start[i])
-        if bank_idx is not None:
-            s = int(res.start[i]) if res.start is not None else 0
-            rec["bank_index"] = int(bank_idx[i, s])
-            rec["bank_distance"] = float(bank_dist[i, s])
-        if evolve_idx is not None:
-            s = int(res.start[i]) if res.start is not None else 0
-            rec["evolve_generations"], rec["evolve_population"] = args.evolve, args.evolve_population
-            rec["evolve_index"] = int(evolve_idx[i, s])
-            rec["evolve_distance"] = float(evolve_dist[i, s])
-        if pitch is not None:
-            rec["voiced"] = bool(pitch.voiced[i])
-            rec["estimated_midi"] = float(pitch.midi[i]) if rec["voiced"] else None
-            rec["pitch_confidence"] = float(pitch.confidence[i])
-        return rec
-
-    if args.split:
-        write_notes(args, files, rate, seg, whole, in_rates, in_lengths, res.audio, record)
-        return
-    if args.resample:
-        from inverse_audio_synthesis_amd.resample import resample
-        audio = [None] * N
-        for sr in sorted(set(in_rates)):
-            idx = [i for i, r in enumerate(in_rates) if r == sr]
-            back = resample(res.audio[idx].contiguous(), rate, sr).cpu().numpy()
-            for k, i in enumerate(idx):
-                audio[i] = back[k]
-    else:
-        audio = res.audio.cpu().numpy()
-    for i, f in enumerate(files):
-        name = os.path.splitext(os.path.basename(f))[0]
-        rec = record(i, os.path.basename(f))
-        if args.resample:
-            rec["input_rate"], rec["synth_rate"] = int(in_rates[i]), rate
-        with open(os.path.join(args.out, name + ".params.json"), "w") as fh:
-            json.dump(rec, fh, indent=1)
-        write_wav(os.path.join(args.out, name + ".match.wav"), audio[i], in_rates[i] if args.resample else rate)
-        print(json.dumps({"input": rec["input"], "initial_loss": rec["initial_loss"], "final_loss": rec["final_loss"]}),
-              flush=True)
+    make_docs = notes_docs if args.split else file_docs
+    audio, docs, lines = make_docs(args, files, rate, tg, res, prov)
+    write_outputs(args, files, rate, tg, audio, docs, lines)
 
 
 if __name__ == "__main__":

@@ -228,6 +228,34 @@ def test_search_end_to_end(lib, dev):
     assert (r.history == 0.0).all()
 
 
+def test_a_start_scores_as_its_bank_voice(lib, dev):
+    """B = 4, N = 2, M = 8, G = 1, k = 2, S = 2.  The starts are voices of a two-batch ``SpectralBank``, start s a bank item
+    of row s, so it is rendered at the row it had in the bank: its distance among the elites is the bank's distance for
+    that pair, bit for bit (one scoring path).  Each sound's target is one of its starts' own render at 0.97 of its
+    level, so that this start is an elite with a distance above 0; the other start is checked when it is an elite too."""
+    from inverse_audio_synthesis_amd.evolve import evolve_search
+    from inverse_audio_synthesis_amd.retrieval import SpectralBank
+    v, loss = _voice(dev), _mel(dev)
+    B, N, M, k = 4, 2, 8, 2
+    bank = SpectralBank(v, loss, [3, 9])
+    item = torch.tensor([[4, 1], [0, 5]], device=dev)       # start s of sound n: a bank item m with m % B == s
+    near = [0, 1]                                           # the start sound n's target is made from
+    audio = torch.cat([v.render(bank.params01[j * B:(j + 1) * B], normalize=True) for j in range(2)])
+    target = 0.97 * audio[[int(item[n, near[n]]) for n in range(N)]]
+    r = evolve_search(v, loss, target_audio=target, generations=1, population=M, elites=k,
+                      init_params01=bank.params01[item], seed=5)
+    d = bank.distances(loss.target(target))
+    for n in range(N):
+        elites = r.idx[n].tolist()
+        assert near[n] in elites, (n, elites, r.dist[n].tolist())
+        for e, m in enumerate(elites):
+            if m < 2:                                       # candidate m < S of generation 0 is start m
+                bm = int(item[n, m])
+                got, want = r.dist.view(torch.int32)[n, e], d.view(torch.int32)[n, bm]
+                assert torch.equal(got, want), (n, m, r.dist[n, e], d[n, bm])
+                assert m != near[n] or 0.0 < float(d[n, bm]) < float("inf")
+
+
 def test_search_improves_the_fit(lib, dev):
     """Only the three mixer levels are free (tests/test_match_gpu.py::test_matcher_descends_on_mixer_levels), M = 32,
     G = 10, seed 0, the other settings at their defaults: the best distance after the last generation is strictly below
