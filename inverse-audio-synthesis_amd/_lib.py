@@ -194,7 +194,10 @@ def _bind(lib, table):
 
 def load_diag():
     """The diagnostic build of the same sources (csrc/libias_hip_diag.so, -DIAS_DIAG: environment switches live,
-    superseded kernels and ``ias_vicreg_set_form`` compiled in; include/ias_hip_diag.h).  A SEPARATE library instance:
+    superseded kernels and ``ias_vicreg_set_form`` compiled in; include/ias_hip_diag.h).  The rule of the split is at the
+    top of csrc/ias_common.h: what only a switch reaches is launched inside ``if constexpr (kIasDiag)``, so the product
+    library (250 kernels) holds no kernel its dispatch cannot reach and this one holds those and 39 more (289; the
+    inventory is pinned by tests/test_capi_symbols.py).  A SEPARATE library instance:
     nothing the package does goes through it unless a test or a diagnostic script asks for it (``use_library``)."""
     global _diag
     if _diag is None:

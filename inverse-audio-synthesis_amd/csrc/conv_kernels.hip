@@ -605,7 +605,8 @@ __global__ __launch_bounds__(CV_THREADS) void stem_fwd_kernel(const float* __res
   }
 }
 
-#ifdef IAS_DIAG   // the VALU / LDS form of the stem weight gradient: superseded by stem_bwd_weight_mfma_kernel, diagnostics only
+// The VALU / LDS form of the stem weight gradient: superseded by stem_bwd_weight_mfma_kernel, instantiated by the diagnostic
+// library only (stem_backward_weight: IAS_STEM_GW_LDS).
 // partial[chunk][co][ci*9+kh*3+kw]: a workgroup stages 256 positions (27 inputs + COUT cotangents each) in LDS, then
 // thread t < COUT*27 sums its weight element over them; grid (position chunks, B).
 template <int CIN, int COUT>
@@ -651,7 +652,6 @@ __global__ __launch_bounds__(CV_THREADS) void stem_bwd_weight_kernel(const float
   if (t1 < NW) pp[t1] = acc1;
 }
 
-#endif
 // The same weight gradient on the matrix cores: gw[co][tap] = sum over positions of g[co][pos] * xcol[tap][pos] is a
 // 16 x 27 x (B Ho Wo) GEMM.  One wave per (sample, chunk of output rows); per 64 output positions of a row it issues
 // 16 k-steps of v_mfma_f32_16x16x4_f32 for each of the two tap tiles (taps 0..15, 16..26): lane (m, q) supplies
@@ -1196,42 +1196,41 @@ static int stem_backward_weight(const float* x, const float* g, float* gw, float
                                 void* stream_) {
   if (!x || !g || !scratch || B <= 0 || B > 65535 || H <= 0 || W <= 0) return IAS_ERR_ARG;
   const int Ho = ias_conv_out_size(H, 3, 2), Wo = ias_conv_out_size(W, 3, 2);
-#ifdef IAS_DIAG
-  if (ias_diag_env("IAS_STEM_GW_LDS")) {   // the VALU / LDS form (diagnostics)
-    hipLaunchKernelGGL((stem_bwd_weight_kernel<3, 16>), dim3(STEM_CHUNKS_X, B), dim3(CV_THREADS), 0, (hipStream_t)stream_, x,
-                       g, scratch, H, W, Ho, Wo, STEM_CHUNKS_X);
-  } else
-#endif
-  {
-    const int waves = B * STEM_CHUNKS_X, rows_per_chunk = (Ho + STEM_CHUNKS_X - 1) / STEM_CHUNKS_X;
-    // LDS-staged form: strides = 3 and = 1 (mod 32) floats; the input rows reach past the last position a tile reads
-    const int GW = (Wo + 63) / 64 * 64;
-    int XS = 2 * GW + 2 > W + 2 ? 2 * GW + 2 : W + 2, GS = GW;
-    while (XS % 32 != 3) ++XS;
-    while (GS % 32 != 1) ++GS;
-    const size_t lds = (size_t)(STEM_STAGE_THREADS / 64) * (9 * XS + 16 * GS) * sizeof(float);
-    if (GW == 128 && XS <= 320 && lds <= 65536 && !ias_diag_env("IAS_STEM_GW_GATHER")) {
-      // half as many chunks as the gather form: 8 resident waves per CU (LDS) x 256 CUs hold B = 128 samples in one round,
-      // and only the first of a wave's 8 rows is fetched with nothing to hide behind
-      const int sc = STEM_CHUNKS_X / 2, swaves = B * sc, srows = (Ho + sc - 1) / sc;
-      hipLaunchKernelGGL((stem_bwd_weight_stage_kernel<3, 16, 5, 2>),
-                         dim3((swaves + STEM_STAGE_THREADS / 64 - 1) / (STEM_STAGE_THREADS / 64)), dim3(STEM_STAGE_THREADS), lds,
-                         (hipStream_t)stream_, x, g, scratch, B, H, W, Ho, Wo, sc, srows, XS, GS);
-      if (nrows) *nrows = swaves;
-      if (gw)
-        hipLaunchKernelGGL(conv_reduce_partials_kernel, dim3((432 + 3) / 4), dim3(CV_THREADS), 0, (hipStream_t)stream_, scratch,
-                           gw, 432, swaves);
-      return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
-    } else
-    hipLaunchKernelGGL((stem_bwd_weight_mfma_kernel<3, 16>), dim3((waves + CV_THREADS / 64 - 1) / (CV_THREADS / 64)),
-                       dim3(CV_THREADS), 0, (hipStream_t)stream_, x, g, scratch, B, H, W, Ho, Wo, STEM_CHUNKS_X,
-                       rows_per_chunk);
+  // the partial rows are in `scratch`: report them, reduce them where the caller wants the gradient itself
+  auto finish = [&](int rows) {
+    if (nrows) *nrows = rows;
+    if (gw)
+      hipLaunchKernelGGL(conv_reduce_partials_kernel, dim3((432 + 3) / 4), dim3(CV_THREADS), 0, (hipStream_t)stream_, scratch, gw,
+                         432, rows);
+    return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
+  };
+  if constexpr (kIasDiag) {   // IAS_STEM_GW_LDS: the VALU / LDS form
+    if (ias_diag_env("IAS_STEM_GW_LDS")) {
+      hipLaunchKernelGGL((stem_bwd_weight_kernel<3, 16>), dim3(STEM_CHUNKS_X, B), dim3(CV_THREADS), 0, (hipStream_t)stream_, x,
+                         g, scratch, H, W, Ho, Wo, STEM_CHUNKS_X);
+      return finish(B * STEM_CHUNKS_X);
+    }
   }
-  if (nrows) *nrows = B * STEM_CHUNKS_X;
-  if (gw)
-    hipLaunchKernelGGL(conv_reduce_partials_kernel, dim3((432 + 3) / 4), dim3(CV_THREADS), 0, (hipStream_t)stream_, scratch, gw,
-                       432, B * STEM_CHUNKS_X);
-  return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
+  const int waves = B * STEM_CHUNKS_X, rows_per_chunk = (Ho + STEM_CHUNKS_X - 1) / STEM_CHUNKS_X;
+  // LDS-staged form: strides = 3 and = 1 (mod 32) floats; the input rows reach past the last position a tile reads
+  const int GW = (Wo + 63) / 64 * 64;
+  int XS = 2 * GW + 2 > W + 2 ? 2 * GW + 2 : W + 2, GS = GW;
+  while (XS % 32 != 3) ++XS;
+  while (GS % 32 != 1) ++GS;
+  const size_t lds = (size_t)(STEM_STAGE_THREADS / 64) * (9 * XS + 16 * GS) * sizeof(float);
+  if (GW == 128 && XS <= 320 && lds <= 65536 && !ias_diag_env("IAS_STEM_GW_GATHER")) {
+    // half as many chunks as the gather form: 8 resident waves per CU (LDS) x 256 CUs hold B = 128 samples in one round,
+    // and only the first of a wave's 8 rows is fetched with nothing to hide behind
+    const int sc = STEM_CHUNKS_X / 2, swaves = B * sc, srows = (Ho + sc - 1) / sc;
+    hipLaunchKernelGGL((stem_bwd_weight_stage_kernel<3, 16, 5, 2>),
+                       dim3((swaves + STEM_STAGE_THREADS / 64 - 1) / (STEM_STAGE_THREADS / 64)), dim3(STEM_STAGE_THREADS), lds,
+                       (hipStream_t)stream_, x, g, scratch, B, H, W, Ho, Wo, sc, srows, XS, GS);
+    return finish(swaves);
+  }
+  hipLaunchKernelGGL((stem_bwd_weight_mfma_kernel<3, 16>), dim3((waves + CV_THREADS / 64 - 1) / (CV_THREADS / 64)),
+                     dim3(CV_THREADS), 0, (hipStream_t)stream_, x, g, scratch, B, H, W, Ho, Wo, STEM_CHUNKS_X,
+                     rows_per_chunk);
+  return finish(B * STEM_CHUNKS_X);
 }
 extern "C" int ias_stem_backward_weight(const float* x, const float* g, float* gw, float* scratch, int B, int H, int W,
                                         void* stream_) {

@@ -12,16 +12,30 @@
 #define IAS_HD inline
 #endif
 
-// Diagnostic switches.  The product library (libias_hip.so) has one kernel per operation and shape and reads NOTHING from
-// the environment: there ias_diag_env() is the constant NULL, so every alternative behind it -- and the kernels only such
-// an alternative reaches, which are additionally fenced by #ifdef IAS_DIAG -- is compiled out, and the library keeps no
-// mutable global state.  `make diag` builds libias_hip_diag.so from the same sources with -DIAS_DIAG, where
-// the switches are live: scripts/diag, bench.py's `dxd` comparison figure, and the tests that compare a superseded kernel
-// with its replacement load THAT library (inverse-audio-synthesis_amd/_lib.py: load_diag / use_library).
+// Diagnostic switches.  The product library (libias_hip.so) has one kernel per operation and shape, reads NOTHING from
+// the environment and keeps no mutable global state.  `make diag` builds libias_hip_diag.so from the same
+// sources with -DIAS_DIAG, where the switches are live: scripts/diag, bench.py's `dxd` comparison figure, and the tests
+// that compare a superseded kernel with its replacement load THAT library (inverse-audio-synthesis_amd/_lib.py:
+// load_diag / use_library).  The split follows one rule:
+//   kIasDiag        the one compile-time flag, true only under -DIAS_DIAG.
+//   dispatch sites  a launch, hipFuncSetAttribute or occupancy query that ONLY a diagnostic switch can reach stands inside
+//                   `if constexpr (kIasDiag) { ... }`, in one block in front of the product's choice, which follows as
+//                   straight-line code.  A discarded statement instantiates nothing: the product build compiles neither
+//                   the host stub nor the device code of a kernel template named only there: 250 kernels in the product
+//                   library, 289 in the diagnostic one (tests/test_capi_symbols.py holds the inventory; scripts/isa_diff.py
+//                   compares two source trees kernel by kernel).
+//   ias_diag_env()  getenv in the diagnostic library, the constant NULL in the product library.  A switch that selects
+//                   between kernels the product also reaches by shape or alignment stays such a runtime read: both
+//                   kernels ship, and the product build folds the read away.
+//   #ifdef IAS_DIAG only around DEFINITIONS the product build would otherwise emit or export: non-template __global__
+//                   kernels, mutable globals, diagnostic-only extern "C" entry points, the matrix-core STFT's device
+//                   code, and the superseded forms of cmul and its kin.  Never inside a launch if / else.
 #ifdef IAS_DIAG
 #include <stdlib.h>
+constexpr bool kIasDiag = true;
 static inline const char* ias_diag_env(const char* name) { return getenv(name); }
 #else
+constexpr bool kIasDiag = false;
 #define ias_diag_env(name) ((const char*)0)
 #endif
 

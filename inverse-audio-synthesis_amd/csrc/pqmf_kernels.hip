@@ -1204,17 +1204,17 @@ extern "C" int ias_pqmf_analysis(const float* x, const float* H, const float* pa
     const long long wgs = (ntiles + PQ_THREADS / 64 - 1) / (PQ_THREADS / 64);
     const long long res = pqmf_resident_blocks();
     const int grid = (int)(wgs < res ? wgs : res);
-    // (diagnostic library: IAS_PQMF_MOD_WINDOW=1 takes the 96-register window form of rounds 3-4; same bits)
-    const bool window = ias_diag_env("IAS_PQMF_MOD_WINDOW") != nullptr;
-    if (window) {
-#ifdef IAS_DIAG
-      if (mean) hipLaunchKernelGGL(pqmf_analysis_mod_kernel<true>, dim3(grid), dim3(PQ_THREADS), 0, stream, x, modtab, z, mean,
-                                   stdv, rowpeak, T, L, tiles_x, (int)ntiles, zvec);
-      else hipLaunchKernelGGL(pqmf_analysis_mod_kernel<false>, dim3(grid), dim3(PQ_THREADS), 0, stream, x, modtab, z, mean,
-                              stdv, rowpeak, T, L, tiles_x, (int)ntiles, zvec);
-#endif
-    } else if (mean) hipLaunchKernelGGL(pqmf_analysis_mods_kernel<true>, dim3(grid), dim3(PQ_THREADS), 0, stream, x, modtab, z, mean,
-                                        stdv, rowpeak, T, L, tiles_x, (int)ntiles, zvec);
+    if constexpr (kIasDiag) {   // IAS_PQMF_MOD_WINDOW=1: the 96-register window form of rounds 3-4; same bits
+      if (ias_diag_env("IAS_PQMF_MOD_WINDOW") != nullptr) {
+        if (mean) hipLaunchKernelGGL(pqmf_analysis_mod_kernel<true>, dim3(grid), dim3(PQ_THREADS), 0, stream, x, modtab, z, mean,
+                                     stdv, rowpeak, T, L, tiles_x, (int)ntiles, zvec);
+        else hipLaunchKernelGGL(pqmf_analysis_mod_kernel<false>, dim3(grid), dim3(PQ_THREADS), 0, stream, x, modtab, z, mean,
+                                stdv, rowpeak, T, L, tiles_x, (int)ntiles, zvec);
+        return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
+      }
+    }
+    if (mean) hipLaunchKernelGGL(pqmf_analysis_mods_kernel<true>, dim3(grid), dim3(PQ_THREADS), 0, stream, x, modtab, z, mean,
+                                 stdv, rowpeak, T, L, tiles_x, (int)ntiles, zvec);
     else hipLaunchKernelGGL(pqmf_analysis_mods_kernel<false>, dim3(grid), dim3(PQ_THREADS), 0, stream, x, modtab, z, mean,
                             stdv, rowpeak, T, L, tiles_x, (int)ntiles, zvec);
   } else if (!force_valu && K == 63 && (N == 3 || N == 64) && T >= 4 && (T & 3) == 0 && ((uintptr_t)x & 15) == 0 &&

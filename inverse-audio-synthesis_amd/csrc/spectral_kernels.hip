@@ -1975,7 +1975,10 @@ static int grad_frames_launch(const float* audio, const float* tables, const int
   } while (0)
 #define IAS_SGW_PICK(MEL, SPAN)                                                                                    \
   do {                                                                                                             \
-    if (n_fft == 512) IAS_SGW_LAUNCH(9, MEL, SPAN);                                                                \
+    if (n_fft == 512) {   /* spans of linear bins are stft_grad512_kernel's (above): only IAS_STFT_V1 brings them here */ \
+      if constexpr (kIasDiag || MEL || !SPAN) IAS_SGW_LAUNCH(9, MEL, SPAN);                                        \
+      else return IAS_ERR_UNSUPPORTED;                                                                             \
+    }                                                                                                              \
     else if (n_fft == 1024) IAS_SGW_LAUNCH(10, MEL, SPAN);                                                         \
     else IAS_SGW_LAUNCH(11, MEL, SPAN);                                                                            \
   } while (0)
@@ -2285,10 +2288,12 @@ extern "C" int ias_stft(const float* audio, const float* tables, const float* mt
   } while (0)
 #define IAS_STFT2_LAUNCH(MEL, LOSS)                                                                                \
   do {                                                                                                             \
-    if (waves2 == 4) IAS_STFT2_LAUNCHW(4, MEL, LOSS);                                                              \
-    else if (waves2 == 5) IAS_STFT2_LAUNCHW(5, MEL, LOSS);                                                         \
-    else if (waves2 == 8) IAS_STFT2_LAUNCHW(8, MEL, LOSS);                                                         \
-    else IAS_STFT2_LAUNCHW(10, MEL, LOSS);                                                                         \
+    if constexpr (kIasDiag) {   /* IAS_STFT2_WAVES = 4, 5, 10 */                                                   \
+      if (waves2 == 4) { IAS_STFT2_LAUNCHW(4, MEL, LOSS); break; }                                                 \
+      if (waves2 == 5) { IAS_STFT2_LAUNCHW(5, MEL, LOSS); break; }                                                 \
+      if (waves2 == 10) { IAS_STFT2_LAUNCHW(10, MEL, LOSS); break; }                                               \
+    }                                                                                                              \
+    IAS_STFT2_LAUNCHW(8, MEL, LOSS);                                                                               \
   } while (0)
 #define IAS_STFT2_LAUNCHH(LOSS)                                                                                    \
   do {                                                                                                             \
@@ -2325,11 +2330,18 @@ extern "C" int ias_stft(const float* audio, const float* tables, const float* mt
     if (loss_mode == 2) hipLaunchKernelGGL((stft_kernel<LOG2N, WAVES, true>), grid, block, lds, stream, a);        \
     else hipLaunchKernelGGL((stft_kernel<LOG2N, WAVES, false>), grid, block, lds, stream, a);                      \
   } while (0)
-  if (n_fft == 512) IAS_STFT_LAUNCH(9, 4);
-  else if (n_fft == 1024) {
-    if (stft_waves(n_fft) == 10) IAS_STFT_LAUNCH(10, 10); else if (stft_waves(n_fft) == 8) IAS_STFT_LAUNCH(10, 8); else IAS_STFT_LAUNCH(10, 4);
-  }
-  else { if (stft_waves(n_fft) == 12) IAS_STFT_LAUNCH(11, 12); else IAS_STFT_LAUNCH(11, 4); }
+  // one wave count per n_fft: 4 / 4 / 12 (stft_waves); IAS_STFT_WAVES = 8, 10 (n_fft 1024) or 4 (n_fft 2048) picks another
+  do {
+    if constexpr (kIasDiag) {
+      const int waves = stft_waves(n_fft);
+      if (n_fft == 1024 && waves == 10) { IAS_STFT_LAUNCH(10, 10); break; }
+      if (n_fft == 1024 && waves == 8) { IAS_STFT_LAUNCH(10, 8); break; }
+      if (n_fft == 2048 && waves == 4) { IAS_STFT_LAUNCH(11, 4); break; }
+    }
+    if (n_fft == 512) IAS_STFT_LAUNCH(9, 4);
+    else if (n_fft == 1024) IAS_STFT_LAUNCH(10, 4);
+    else IAS_STFT_LAUNCH(11, 12);
+  } while (0);
 #undef IAS_STFT_LAUNCH
   return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
 }

@@ -890,14 +890,14 @@ extern "C" int ias_vicreg_set_form(int form) {
   g_vicreg_form = form;
   return IAS_OK;
 }
-static bool vicreg_batch_side(int Kpad, int D) {
+static bool vicreg_feature_side_forced() {
   static const bool env_dxd = ias_diag_env("IAS_VICREG_DXD") != nullptr && atoi(ias_diag_env("IAS_VICREG_DXD")) != 0;
-  const bool want = g_vicreg_form < 0 ? !env_dxd : g_vicreg_form == 1;
-  return want && D >= 8 && (D & 7) == 0 && Kpad <= D;
+  return g_vicreg_form < 0 ? env_dxd : g_vicreg_form == 0;
 }
 #else
-static bool vicreg_batch_side(int Kpad, int D) { return D >= 8 && (D & 7) == 0 && Kpad <= D; }
+static constexpr bool vicreg_feature_side_forced() { return false; }
 #endif
+static bool vicreg_batch_side(int Kpad, int D) { return !vicreg_feature_side_forced() && D >= 8 && (D & 7) == 0 && Kpad <= D; }
 
 static VicregWs vicreg_ws(int B, int D) {
   VicregWs w;

@@ -172,7 +172,6 @@ __global__ __launch_bounds__(VOICE_THREADS) void voice_modmix_kernel(
   }
 }
 
-#ifdef IAS_DIAG   // measured slower in the step than the three slim kernels: diagnostic library only
 // ---- the whole control pass of a voice in ONE workgroup (round 5) -------------------------------------------------
 // voice_env_kernel -> voice_lfo_kernel -> voice_modmix_kernel are three dependent launches whose intermediate rows go through
 // HBM, and their pow / cos / fmodf were the device math library's (pow: ~300 fp64-rate instructions): 33 us alone, and
@@ -184,7 +183,16 @@ __global__ __launch_bounds__(VOICE_THREADS) void voice_modmix_kernel(
 #define CTLF_THREADS 1024
 #define CTLF_WAVES (CTLF_THREADS / 64)
 #define CTLF_LFO_WAVES (CTLF_WAVES / 2)      // waves per LFO in the scan phase
+// Measured slower in the step than the three slim kernels: declared everywhere, so that
+// voice_control_launch can name it in its fenced block, DEFINED in the diagnostic library only (ias_common.h).
+__global__ void voice_control_fused_kernel(const float* __restrict__ params01, float* __restrict__ sig,
+                                           float* __restrict__ ctrl, IasVoiceConst* __restrict__ vconst,
+                                           float* __restrict__ dbg, int Tc, float control_rate);
+static size_t voice_control_fused_lds(int Tc) {
+  return sizeof(double) * (IAS_CTL_TAB_DOUBLES + 2 * (size_t)Tc) + sizeof(float) * 8 * (size_t)Tc;
+}
 
+#ifdef IAS_DIAG
 __device__ const double g_ctl_tab[IAS_CTL_TAB_DOUBLES] = IAS_CTL_TAB_INIT;
 
 __global__ __launch_bounds__(CTLF_THREADS) void voice_control_fused_kernel(
@@ -320,10 +328,6 @@ __global__ __launch_bounds__(CTLF_THREADS) void voice_control_fused_kernel(
     }
   }
 }
-static size_t voice_control_fused_lds(int Tc) {
-  return sizeof(double) * (IAS_CTL_TAB_DOUBLES + 2 * (size_t)Tc) + sizeof(float) * 8 * (size_t)Tc;
-}
-
 #endif
 
 // -------------------------------------------------------------------- audio rate
@@ -959,23 +963,23 @@ static int voice_control_launch(const float* params01, float* ctrl, void* vconst
   // (diagnostic library: IAS_VOICE_CTRL=fused / libm pick the one-workgroup-per-voice kernel / the round-1 kernels with the
   // device math library's pow / cos / fmodf at any size)
   const char* form = ias_diag_env("IAS_VOICE_CTRL");
+  if constexpr (kIasDiag) {
+    // (one workgroup per voice while its rows fit the LDS of a CU: 48 bytes per control sample + the 4 KB table, Tc <= ~3200)
+    const size_t flds = voice_control_fused_lds(Tc);
+    if (flds <= 156 * 1024 && form != nullptr && form[0] == 'f') {
+      static bool attr_set = false;                          // (idempotent: a race sets it twice)
+      if (!attr_set) {
+        if (hipFuncSetAttribute((const void*)voice_control_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess)
+          return IAS_ERR_LAUNCH;
+        attr_set = true;
+      }
+      hipLaunchKernelGGL(voice_control_fused_kernel, dim3(B), dim3(CTLF_THREADS), flds, stream, params01, sig, ctrl,
+                         (IasVoiceConst*)vconst, dbg, Tc, (float)control_rate);
+      return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
+    }
+  }
   if (form == nullptr && ias_voice_control_slim_ok(Tc, control_rate))
     return ias_voice_control_slim_launch(params01, ctrl, vconst, sig, dbg, B, Tc, control_rate, stream);
-#ifdef IAS_DIAG
-  // (one workgroup per voice while its rows fit the LDS of a CU: 48 bytes per control sample + the 4 KB table, Tc <= ~3200)
-  const size_t flds = voice_control_fused_lds(Tc);
-  if (flds <= 156 * 1024 && form != nullptr && form[0] == 'f') {
-    static bool attr_set = false;                          // (idempotent: a race sets it twice)
-    if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)voice_control_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess)
-        return IAS_ERR_LAUNCH;
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(voice_control_fused_kernel, dim3(B), dim3(CTLF_THREADS), flds, stream, params01, sig, ctrl,
-                       (IasVoiceConst*)vconst, dbg, Tc, (float)control_rate);
-    return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
-  }
-#endif
   // control buffers longer than the slim kernels take: the round-1 kernels (device math library, rows through HBM)
   const size_t lds = sizeof(double) * (VOICE_WAVES + (size_t)Tc);
   if (lds > 160 * 1024) return IAS_ERR_UNSUPPORTED;

@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ counters of the PQMF analysis kernel alone (scripts/diag/time_pqmf.py).  usage: bash scripts/diag/pmc_pqmf.sh <tag> [ENV=.. ...]
 tag=${1:-x}; shift
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/../.." && pwd)
 O=$R/gpurun_out/pmcq_$tag
 mkdir -p $O
 for kv in "$@"; do export "$kv"; done
@@ -10,9 +10,9 @@ i=0
 for set in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES" \
            "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT" \
            "SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU" \
-           "GRBM_GUI_ACTIVE" "FETCH_SIZE" "WRITE_SIZE"; do
+           "GRBM_GUI_ACTIVE" "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VMEM_WR"; do
   i=$((i+1))
-  rocprofv3 --pmc $set --kernel-trace -d $O/p$i -o out --output-format csv -- python3 $R/scripts/diag/time_pqmf.py > $O/p$i.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc $set --kernel-trace -d $O/p$i -o out --output-format csv -- python3 $R/scripts/diag/time_pqmf.py > $O/p$i.log 2>&1 || { echo "$O/p$i.log: failed, stopping"; tail -20 $O/p$i.log; exit 1; }
 done
 python3 - > $O/summary.txt <<PY
 import csv, glob, collections

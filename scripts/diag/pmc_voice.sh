@@ -2,7 +2,7 @@
 # SQ / LDS / TCP counters of the audio-rate render kernel alone (scripts/diag/time_voice.py, eager launches).
 # usage (GPU box): bash scripts/diag/pmc_voice.sh <tag>       -> gpurun_out/pmcv_<tag>/summary.txt
 tag=${1:-x}
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/../.." && pwd)
 O=$R/gpurun_out/pmcv_$tag
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
@@ -12,9 +12,9 @@ for set in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_VMEM" \
            "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE" "TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum" "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
-  EAGER=1 K=6 rocprofv3 --pmc $set --kernel-trace -d $O/p$i -o out --output-format csv -- python3 $R/scripts/diag/time_voice.py > $O/p$i.log 2>&1
+  EAGER=1 K=6 timeout -k 10 300 rocprofv3 --pmc $set --kernel-trace -d $O/p$i -o out --output-format csv -- python3 $R/scripts/diag/time_voice.py > $O/p$i.log 2>&1 || { echo "$O/p$i.log: failed, stopping"; tail -20 $O/p$i.log; exit 1; }
 done
-EAGER=1 K=20 rocprofv3 --kernel-trace --stats -d $O/stats -o out --output-format csv -- python3 $R/scripts/diag/time_voice.py > $O/stats.log 2>&1
+EAGER=1 K=20 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats -o out --output-format csv -- python3 $R/scripts/diag/time_voice.py > $O/stats.log 2>&1 || { echo "$O/stats.log: failed, stopping"; tail -20 $O/stats.log; exit 1; }
 python3 - > $O/summary.txt <<PY
 import csv, glob, collections
 agg = collections.defaultdict(lambda: collections.defaultdict(list))

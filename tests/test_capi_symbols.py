@@ -65,6 +65,50 @@ def test_product_library_reads_no_environment_and_keeps_no_switch(lib):
             assert "getenv" not in open(os.path.join(csrc, f)).read(), f
 
 
+# kernels only a diagnostic switch launches (the site table of DESIGN.md section 1), as the prefix of their host stub
+DIAG_ONLY_KERNELS = (
+    "stft2_kernel<4,", "stft2_kernel<5,", "stft2_kernel<10,",                   # IAS_STFT2_WAVES
+    "stft_kernel<10, 10,", "stft_kernel<10, 8,", "stft_kernel<11, 4,",          # IAS_STFT_WAVES
+    "stft_grad_wave_kernel<9, false, true,",                                    # IAS_STFT_V1 (spans of linear bins, n_fft 512)
+    "stft_mfma_kernel<",                                                        # IAS_STFT_MFMA
+    "pqmf_analysis_mod_kernel<",                                                # IAS_PQMF_MOD_WINDOW
+    "stem_bwd_weight_kernel<",                                                  # IAS_STEM_GW_LDS
+    "voice_control_fused_kernel(",                                              # IAS_VOICE_CTRL=fused
+)
+# kernels the product dispatch names where a diagnostic alternative stands in front of them
+PRODUCT_KERNELS = (
+    "stft2_kernel<8, true, 1, 1>", "stft2_kernel<8, false, 2, 2>", "stft2h_kernel<8, 1>",
+    "stft_kernel<10, 4,", "stft_kernel<11, 12,", "stft_kernel<9, 4,",
+    "stft_grad_wave_kernel<9, true, true,", "stft_grad_wave_kernel<9, false, false,", "stft_grad512_kernel<8, false>",
+    "pqmf_analysis_mods_kernel<true>", "pqmf_analysis_mods_kernel<false>",
+    "stem_bwd_weight_stage_kernel<3, 16, 5, 2>", "stem_bwd_weight_mfma_kernel<3, 16>",
+    "voice_env_kernel(", "voice_lfo_kernel(", "voice_modmix_kernel(",
+)
+
+
+def _device_stubs(path):
+    import subprocess
+    out = subprocess.run(["nm", "-C", path], stdout=subprocess.PIPE, text=True, check=True).stdout
+    return {l.split("__device_stub__", 1)[1] for l in out.split("\n") if "__device_stub__" in l}
+
+
+def test_product_library_compiles_only_the_kernels_its_dispatch_reaches(lib):
+    """csrc/ias_common.h: a launch only a diagnostic switch reaches stands inside `if constexpr (kIasDiag)`, so the product
+    library holds neither the host stub nor the device code of such a kernel; the diagnostic library holds every kernel
+    of the product library and the diagnostic ones on top."""
+    from inverse_audio_synthesis_amd import _lib
+    _lib.load_diag()
+    product, diag = _device_stubs(_lib.LIB_PATH), _device_stubs(_lib.DIAG_LIB_PATH)
+    assert len(product) > 100 and len(diag) > len(product)
+    for prefix in DIAG_ONLY_KERNELS:
+        assert not [s for s in product if s.startswith(prefix)], f"{prefix} is in the product library"
+        assert [s for s in diag if s.startswith(prefix)], f"{prefix} is not in the diagnostic library"
+    for prefix in PRODUCT_KERNELS:
+        assert [s for s in product if s.startswith(prefix)], f"{prefix} is not in the product library"
+        assert [s for s in diag if s.startswith(prefix)], f"{prefix} is not in the diagnostic library"
+    assert product <= diag, sorted(product - diag)
+
+
 def test_diagnostic_library_exports_the_product_abi_plus_its_own(lib):
     from inverse_audio_synthesis_amd import _lib
     diag = _lib.load_diag()            # binds every product symbol and every diagnostic-only symbol, or raises

@@ -133,12 +133,15 @@ def test_mrstft_cached_targets_equal_recomputed(lib, dev):
         m(x)
 
 
-@pytest.mark.parametrize("env", [{"IAS_STFT_MFMA": "1"}, {"IAS_STFT_V1": "1"}])
+@pytest.mark.parametrize("env", [{"IAS_STFT_MFMA": "1"}, {"IAS_STFT_V1": "1"},
+                                 {"IAS_STFT2_WAVES": "4"}, {"IAS_STFT2_WAVES": "5"}, {"IAS_STFT2_WAVES": "10"},
+                                 {"IAS_STFT_V1": "1", "IAS_STFT_WAVES": "10"}, {"IAS_STFT_V1": "1", "IAS_STFT_WAVES": "8"}])
 def test_alternative_stft_kernels_in_a_child_process(lib, dev, env):
     """The DIAGNOSTIC library (csrc/libias_hip_diag.so; the product library reads nothing from the environment and does
     not contain the matrix-core kernel) reads the kernel choice once per process from the environment: the opt-in
-    matrix-core kernel (IAS_STFT_MFMA=1) and the round-2 kernel (IAS_STFT_V1=1) are checked in a
-    child process (a fresh interpreter, not a re-exec of this one; IAS_HIP_LIB points the package at the diagnostic
+    matrix-core kernel (IAS_STFT_MFMA=1), the round-2 kernel (IAS_STFT_V1=1) and the other wave
+    counts of both radix-8 kernels (IAS_STFT2_WAVES, IAS_STFT_WAVES: launches that stand inside `if constexpr (kIasDiag)`,
+    csrc/ias_common.h) are checked in a child process (a fresh interpreter, not a re-exec of this one; IAS_HIP_LIB points the package at the diagnostic
     library) against the same oracle and tolerances as the default kernel: mel spectrogram, raw power
     spectrogram with a hop that is not a multiple of four samples, and the fused mel-L1 loss."""
     import os
