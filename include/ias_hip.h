@@ -508,6 +508,51 @@ int ias_segment_scatter(const float* notes, int N, int L, const int* row, const 
                         const unsigned char* faded, int S, int T, int fade, float inv_fade, const float* gain, float* out,
                         void* stream);
 
+/* ---- Envelope stage of sound matching (envelope.envelope_frames / envelope_score / fit_envelope, match_audio.py
+ * --envelope): the RMS envelope of a target and the distance of the Voice's own envelope law to it, the scorer of a
+ * population search over keyboard.duration and one ADSR (scored candidates are selected with ias_topk_merge and refitted
+ * with ias_evolve_update, as the spectral search's are).  The reference never analyses its targets, so this has no
+ * counterpart there.  Every entry: one launch, no workspace, no atomics on global memory, no global state: capturable.
+ * Nothing is launched on a refusal.
+ * ias_envelope_num_frames (HOST only): F = (T - W) / hop + 1 (integer division), the number of frames of a row; a negative
+ *   IAS_ERR_ARG when a size is < 1 or T < W (not even one frame).
+ * ias_envelope_frames: audio [B, T] (device fp32, row-major, row stride T) -> rms [B, F] (device fp32).  Frame f of row b
+ *   uses x[f hop .. f hop + W):
+ *     c = gcd(W, hop); block k of the frame is its samples [k c, (k + 1) c), k = 0 .. W / c - 1;
+ *     s_k = the block's sum of squares in fp64: one chain over its samples in ascending order from +0,
+ *       s = fma((double)x, (double)x, s) (the square of an fp32 value is exact in fp64, so the fused step rounds once, as
+ *       the sum does);
+ *     S = one fp64 chain over s_k in ascending k from +0;
+ *     rms[b,f] = fp32(sqrt(S / (double)W)): quotient and root in fp64, rounded to fp32 once.
+ *   The order is a function of W and hop alone.  Frames that overlap share whole blocks (W = 1024, hop = 256: four blocks
+ *   of 256 per frame), so a sample is read once and squared once.  A frame's bits depend on its W samples and the scalars
+ *   alone: not on B, the row, its 4-byte phase or the launch shape.  A row of zeros gives +0.
+ *   IAS_ERR_ARG: null pointers, B, T, W or hop < 1, T < W.  IAS_ERR_UNSUPPORTED: B > 65535.
+ * ias_envelope_score: env [N, F] (device fp32: a sound's envelope, frame f at t_f = t0 + f dt seconds, product and sum in
+ *   fp64), cand [N, M, 6] (device fp32 in 0..1) -> dist [N, M] (device fp32).  A candidate's columns are duration, attack,
+ *   decay, sustain, release, alpha of the Voice in 0..1; in units, by the Voice's parameter table (curve 0.5: a square;
+ *   curve 1: linear), in fp64 with u^2 formed first:
+ *     dur = 0.01 + 3.99 u0^2, att = 2 u1^2, dec = 2 u2^2, sus = u3, rel = 5 u4^2, alpha = 0.1 + 5.9 u5.
+ *   The model is the Voice's ADSR (torchsynth's) in continuous time without its epsilon terms, all in fp64:
+ *     ramp(x, L) = L > 0 ? clamp(x / L, 0, 1) : (x >= 0 ? 1 : 0);   a' = min(att, dur);   d' = min(max(dur - att, 0), dec);
+ *     A(t) = (ramp(t, a')^alpha ((1 - sus) (1 - ramp(t - a', d'))^alpha + sus)) (1 - ramp(t - dur, rel))^alpha,
+ *   each power pow() of a base in [0, 1], where a base of exactly 0 or 1 gives itself; products in the order written.
+ *     S_aA = sum_f env[f] A(t_f), S_AA = sum_f A(t_f)^2, S_aa = sum_f env[f]^2: each one fp64 chain in ascending f from +0,
+ *       product rounded, then the sum (no FMA);
+ *     D = S_AA S_aa;  dist = fp32(D > 0 ? clamp(1 - S_aA^2 / D, 0, 1) : D == 0 ? 1 : NaN).
+ *   dist is 1 - cos^2 of the angle between env and the model: invariant to the gain of either, in [0, 1].  A silent row
+ *   (or a model that is 0 at every frame) scores exactly 1; a NaN in env makes D a NaN and every dist of the row NaN, which
+ *   ias_topk_merge ranks last.  A candidate's bits depend on its six values, its row of env and the scalars alone: not on
+ *   N, M, its position in the population or the launch shape.  One wave per sound and 64 candidates, the row of env staged
+ *   in LDS once.
+ *   IAS_ERR_ARG: null pointers, N, M or F < 1, t0 not finite, dt not finite or <= 0 (a NaN included).
+ *   IAS_ERR_UNSUPPORTED: a row of env over the kernel's LDS budget of 64 KB, 4 F > 65536 bytes (F <= 16384: 95 s of
+ *   envelope at 44.1 kHz and hop 256); N > 65535. */
+long long ias_envelope_num_frames(int T, int W, int hop);
+int ias_envelope_frames(const float* audio, int B, int T, int W, int hop, float* rms, void* stream);
+int ias_envelope_score(const float* env, const float* cand, int N, int M, int F, double t0, double dt, float* dist,
+                       void* stream);
+
 /* ---- Band-limited resampling (resample.resample / resample.Resample, match_audio.py --resample): torchaudio's
  * windowed-sinc polyphase resampler, torchaudio.functional.resample (_get_sinc_resample_kernel +
  * _apply_sinc_resample_kernel), which the reference depends on (its requirements.txt).

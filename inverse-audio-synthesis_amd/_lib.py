@@ -101,6 +101,9 @@ SYMBOLS = {
     "ias_onset_pick": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P]),
     "ias_segment_gather": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P]),
     "ias_segment_scatter": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P]),
+    "ias_envelope_num_frames": (_LL, [_I, _I, _I]),
+    "ias_envelope_frames": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "ias_envelope_score": (_I, [_P, _P, _I, _I, _I, _c.c_double, _c.c_double, _P, _P]),
     "ias_resample_plan": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
     "ias_resample_build_taps": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
     "ias_resample_out_len": (_LL, [_LL, _I, _I]),
@@ -196,7 +199,7 @@ def load_diag():
     """The diagnostic build of the same sources (csrc/libias_hip_diag.so, -DIAS_DIAG: environment switches live,
     superseded kernels and ``ias_vicreg_set_form`` compiled in; include/ias_hip_diag.h).  The rule of the split is at the
     top of csrc/ias_common.h: what only a switch reaches is launched inside ``if constexpr (kIasDiag)``, so the product
-    library (250 kernels) holds no kernel its dispatch cannot reach and this one holds those and 39 more (289; the
+    library (253 kernels) holds no kernel its dispatch cannot reach and this one holds those and 39 more (292; the
     inventory is pinned by tests/test_capi_symbols.py).  A SEPARATE library instance:
     nothing the package does goes through it unless a test or a diagnostic script asks for it (``use_library``)."""
     global _diag

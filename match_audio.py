@@ -4,6 +4,7 @@
     python match_audio.py in1.wav in2.wav --steps 200 --out DIR [--init center|random|bank] [--starts S]
                           [--bank-batches NB] [--bank-stream CHUNK] [--evolve G] [--evolve-population M]
                           [--evolve-elites K] [--evolve-sigma S0] [--pitch] [--pitch-lo MIDI] [--pitch-hi MIDI]
+                          [--envelope] [--envelope-generations G] [--envelope-population M]
                           [--split] [--onset-delta D] [--max-notes K] [--fade-ms MS] [--loss LOSS] [key=value ...]
 
 ``key=value`` are config overrides as for pretrain.py / audio_to_params.py (``torchsynth.rate``,
@@ -28,6 +29,13 @@ the same loss as the bank and ``--seed``; its ``--starts`` best of ``--evolve-el
 ``--pitch-lo`` and ``--pitch-hi`` (MIDI, default 21..108) off the waveform and ``pitch.retune`` moves ``keyboard.midi_f0``
 of every start ``--init`` produced onto it, before ``--evolve`` and the fit; unvoiced targets keep their starts.  The
 JSON record gains ``estimated_midi`` (null when unvoiced), ``voiced`` and ``pitch_confidence``.
+``--envelope`` (off by default) reads how long each target sounds and how it rises and falls: ``envelope.fit_envelope``
+fits the Voice's envelope law (duration, attack, decay, sustain, release, alpha) to the target's RMS envelope with
+``--envelope-generations`` generations of ``--envelope-population`` candidates per sound and ``--seed``, and
+``envelope.reshape`` writes it into ``keyboard.duration``, ``adsr_1`` and ``adsr_2`` of every start, after ``--pitch`` and
+before ``--evolve`` and the fit; silent targets keep their starts.  The JSON record gains ``envelope``: ``sounding``,
+``distance`` and ``start_distance`` (1 - cos^2 between the target's envelope and the law, fitted and at the start) and the
+six fitted values in their own units.
 ``--split`` (off by default) matches a recording note by note.  The files are read whole (after ``--resample``),
 ``onset.detect_onsets`` finds every file's note onsets on the device (``--onset-delta``; at most ``--max-notes`` per file,
 with a warning when there are more) and ``onset.split_notes`` cuts one synth buffer per note from its onset, faded out over
@@ -147,6 +155,7 @@ class Provenance:
     bank: object = None             # (dist, idx) [N, starts] device tensors: the nearest bank voices, or None
     evolve: object = None           # (dist, idx) [N, starts]: the best elites of the evolutionary search, or None
     pitch: object = None            # ``pitch.PitchResult`` of the N sounds, or None
+    envelope: object = None         # ``envelope.EnvelopeFit`` of the N sounds, or None
 
 
 def split_targets(rows, files, rate, T, args):
@@ -195,6 +204,7 @@ def load_targets(args, files, rate, T, dev):
 
 INITS = ("center", "random", "bank")
 BANK_BATCH = 128
+ENVELOPE_ELITES = 16                # ``envelope.fit_envelope``'s default
 
 
 def parse_args(argv=None):
@@ -229,6 +239,12 @@ def parse_args(argv=None):
                     help="estimate each target's note and start keyboard.midi_f0 there (pitch.estimate_pitch / retune)")
     ap.add_argument("--pitch-lo", type=float, default=21.0, metavar="MIDI", help="--pitch: lowest note searched")
     ap.add_argument("--pitch-hi", type=float, default=108.0, metavar="MIDI", help="--pitch: highest note searched")
+    ap.add_argument("--envelope", action="store_true",
+                    help="fit the Voice's envelope law to each target's RMS envelope and start keyboard.duration and both "
+                         "ADSRs there (envelope.fit_envelope / reshape)")
+    ap.add_argument("--envelope-generations", type=int, default=16, metavar="G", help="--envelope: generations searched")
+    ap.add_argument("--envelope-population", type=int, default=512, metavar="M",
+                    help="--envelope: candidates per sound and generation (at least the 16 elites kept)")
     ap.add_argument("--split", action="store_true",
                     help="find the note onsets of every file and match it note by note (onset.detect_onsets / split_notes); "
                          "writes NAME.notes.json and a NAME.match.wav of the file's full length")
@@ -261,6 +277,12 @@ def parse_args(argv=None):
         ap.error("--init center has one start per sound: --starts must be 1")
     if not args.pitch_lo < args.pitch_hi:
         ap.error("--pitch-lo must be below --pitch-hi")
+    if args.envelope_generations < 1:
+        ap.error("--envelope-generations must be >= 1")
+    if args.envelope_population < ENVELOPE_ELITES:
+        ap.error(f"--envelope-population must be >= {ENVELOPE_ELITES}")
+    if args.envelope_population > (1 << 31) // args.envelope_generations:
+        ap.error("--envelope-population x --envelope-generations must not exceed 2^31")
     if not 0.0 < args.onset_delta < float("inf"):
         ap.error("--onset-delta must be finite and > 0")
     if args.max_notes < 1:
@@ -335,6 +357,20 @@ def pitch_stage(args, target, rate, init, prov):
     return retune(init, prov.pitch)
 
 
+def envelope_stage(args, target, rate, init, prov):
+    """--envelope: fit every target's envelope (``prov.envelope``) and write it into its starts."""
+    import torch
+    from inverse_audio_synthesis_amd.envelope import fit_envelope, reshape
+    try:
+        prov.envelope = fit_envelope(target, rate, generations=args.envelope_generations,
+                                     population=args.envelope_population, elites=ENVELOPE_ELITES, seed=args.seed)
+    except ValueError as e:
+        sys.exit(f"match_audio.py: --envelope: {e}")
+    if init is None:                                     # --init center: the centre matrix, so that it can be reshaped
+        init = torch.full((target.shape[0], 78), 0.5, dtype=torch.float32, device=target.device)
+    return reshape(init, prov.envelope)
+
+
 def evolve_stage(args, stage, target, init, prov):
     """--evolve: the search from ``init`` -> its --starts best elites as the starts; ``prov`` names them."""
     from inverse_audio_synthesis_amd.evolve import evolve_search
@@ -364,6 +400,12 @@ def record(args, res, prov, i, name):
         rec["voiced"] = bool(prov.pitch.voiced[i])
         rec["estimated_midi"] = float(prov.pitch.midi[i]) if rec["voiced"] else None
         rec["pitch_confidence"] = float(prov.pitch.confidence[i])
+    if prov.envelope is not None:
+        from inverse_audio_synthesis_amd.envelope import COLUMNS
+        fit = prov.envelope
+        rec["envelope"] = {"sounding": bool(fit.sounding[i]), "distance": float(fit.dist[i]),
+                           "start_distance": float(fit.start_dist[i]),
+                           **{name: float(v) for name, v in zip(COLUMNS, fit.units[i])}}
     return rec
 
 
@@ -442,6 +484,8 @@ def main(argv=None):
     init = initial_starts(args, stage, tg.audio, prov)
     if args.pitch:
         init = pitch_stage(args, tg.audio, rate, init, prov)
+    if args.envelope:
+        init = envelope_stage(args, tg.audio, rate, init, prov)
     if args.evolve > 0:
         init = evolve_stage(args, stage, tg.audio, init, prov)
     res = matcher.fit(tg.audio, init_params01=init, steps=args.steps, return_audio=True)
