@@ -5,9 +5,9 @@ a render that is silent where the target sounds gives no gradient that lengthens
 six numbers (``COLUMNS``), and fitting it to the target's envelope needs no audio render: ``envelope_frames``
 (ias_envelope_frames) takes the RMS per frame, ``envelope_score`` (ias_envelope_score) gives the distance 1 - cos^2 between
 it and the law for a whole population of candidates, and ``fit_envelope`` runs the evolutionary search's loop
-(``evolve.evolve_search``: ias_evolve_sample, ias_topk_merge, ias_evolve_update) with that scorer.  ``reshape`` writes the
-result into the starts of a fit (``match_audio.py --envelope``).  One note per sound is assumed, as
-by ``pitch.estimate_pitch``.
+(``evolve.cross_entropy_search``: ias_evolve_sample, ias_topk_merge, ias_evolve_update) with that scorer.  ``reshape``
+writes the result into the starts of a fit (``match_audio.py --envelope``).  One note per sound is
+assumed, as by ``pitch.estimate_pitch``.
 
 The six parameters are not identifiable one by one (a short note with a long attack has the envelope of a longer note with
 a short one); what the stage finds is an envelope, and ``EnvelopeFit.dist`` says how near it is.
@@ -19,8 +19,8 @@ import torch
 
 from . import _lib
 from . import voice_spec as S
-from .evolve import evolve_sample, evolve_update
-from .retrieval import EMPTY_INDEX, topk_merge
+from .evolve import cross_entropy_search, evolve_sample, evolve_update
+from .retrieval import topk_merge
 
 COLUMNS = ("duration", "attack", "decay", "sustain", "release", "alpha")
 LDS_BUDGET_BYTES = 65536            # ias_envelope_score's LDS budget: a row of env, 4 F bytes (include/ias_hip.h)
@@ -109,7 +109,7 @@ def envelope_score(env, cand, t0, dt, out=None):
 
 
 # The five primitives of ``fit_envelope`` on the device.  The tests pass the same five restated in fp64 numpy on CPU
-# tensors (tests/envelope_model.py), so the search below is one code path for both.
+# tensors (tests/envelope_model.py), so the search is one code path for both; its loop takes the last three from here.
 DEVICE_OPS = SimpleNamespace(frames=envelope_frames, sample=evolve_sample, score=envelope_score, merge=topk_merge,
                              update=evolve_update)
 
@@ -120,13 +120,11 @@ def fit_envelope(audio, sample_rate, W=1024, hop=256, generations=16, population
     """audio [N, T] -> ``EnvelopeFit``: the envelope law nearest to each sound's RMS envelope.
 
     The envelope is ``ops.frames(audio, W, hop)``, frame f at the centre of its window: t0 = (W / 2) / sample_rate,
-    dt = hop / sample_rate.  The search is ``evolve.evolve_search``'s loop with P = 6 and every column free: per sound a
-    Gaussian per column (mean: the start, sigma: ``sigma0``), per generation ``population`` candidates clamp(mean + sigma z,
-    0, 1) scored by ``ops.score``, merged into the ``elites`` best seen so far and the Gaussian moved towards the elites by
-    ``alpha``, sigma kept within [sigma_min, sigma_max].  The start, 0.5 everywhere or ``init01`` [N, 6], is candidate 0 of
-    generation 0, so the result is never worse than the start (``dist <= start_dist``).
+    dt = hop / sample_rate.  The search is ``evolve.cross_entropy_search`` (which also checks the settings) with P = 6,
+    every column free, no ``history`` and ``ops.score`` as the scorer.  The start, 0.5 everywhere or ``init01`` [N, 6], is
+    candidate 0 of generation 0, so the result is never worse than the start (``dist <= start_dist``).
 
-    Per generation: one ``ops.score``, a copy of the elite indices, one ``ops.merge``, one ``ops.update`` and one
+    Per generation: one ``ops.score``, and the loop's copy of the elite indices, ``ops.merge``, ``ops.update`` and
     ``ops.sample`` for the next generation, for all sounds at once.  The host reads nothing back, every buffer is reused,
     and the same seed gives the same bits.  A silent sound scores 1 everywhere and comes back with ``sounding`` False.
     ``ops``: the primitives; the default runs the HIP kernels on device tensors."""
@@ -134,22 +132,8 @@ def fit_envelope(audio, sample_rate, W=1024, hop=256, generations=16, population
         raise ValueError(f"fit_envelope: audio must be [N, T], got {tuple(audio.shape)}")
     if not float(sample_rate) > 0.0:
         raise ValueError(f"fit_envelope: sample_rate must be > 0, got {sample_rate}")
-    G, M, k, P = int(generations), int(population), int(elites), len(COLUMNS)
-    if G < 1:
-        raise ValueError(f"fit_envelope: generations must be >= 1, got {generations}")
-    if M < 1 or M > (1 << 31) // G:
-        raise ValueError(f"fit_envelope: population must be >= 1 and population x generations at most 2^31, got {M} x {G}")
-    if not 1 <= k <= 64 or k > M:
-        raise ValueError(f"fit_envelope: elites must be in 1..64 (ias_topk_merge) and at most the population {M}, got {k}")
-    for name, v in (("sigma0", sigma0), ("sigma_min", sigma_min), ("sigma_max", sigma_max)):
-        if not (0.0 <= float(v) < float("inf")):
-            raise ValueError(f"fit_envelope: {name} must be finite and >= 0, got {v}")
-    if float(sigma_max) < float(sigma_min) or not 0.0 <= float(alpha) <= 1.0:
-        raise ValueError("fit_envelope: need sigma_min <= sigma_max and alpha in [0, 1]")
     audio = audio.detach().to(torch.float32).contiguous()
-    N, dev = audio.shape[0], audio.device
-    if not 1 <= N <= 65535:
-        raise ValueError(f"fit_envelope: 1..65535 sounds per call (ias_topk_merge), got {N}")
+    N, dev, P = audio.shape[0], audio.device, len(COLUMNS)
     if init01 is None:
         start = torch.full((N, P), 0.5, dtype=torch.float32, device=dev)
     else:
@@ -157,35 +141,19 @@ def fit_envelope(audio, sample_rate, W=1024, hop=256, generations=16, population
             raise ValueError(f"fit_envelope: init01 must be [{N}, {P}], got {tuple(init01.shape)}")
         start = init01.detach().to(device=dev, dtype=torch.float32).clamp(0.0, 1.0)
 
-    rms = ops.frames(audio, W, hop)
+    rms = ops.frames(audio, W, hop)                      # first, so that it runs while the host sets the search up
     t0, dt = (int(W) / 2.0) / float(sample_rate), int(hop) / float(sample_rate)
-    free = torch.ones(P, dtype=torch.uint8, device=dev)
-    block = torch.empty((N, M), dtype=torch.float32, device=dev)
-    pop = torch.empty((N, M, P), dtype=torch.float32, device=dev)
-    mean = start.contiguous().clone()
-    sigma = torch.full((N, P), float(sigma0), dtype=torch.float32, device=dev)
-    elite_dist = torch.full((N, k), float("inf"), dtype=torch.float32, device=dev)
-    elite_idx = torch.full((N, k), EMPTY_INDEX, dtype=torch.int64, device=dev)
-    prev_idx = torch.empty_like(elite_idx)
-    elite_params = torch.zeros((N, k, P), dtype=torch.float32, device=dev)
-    prev_params = torch.zeros_like(elite_params)
     start_dist = torch.empty(N, dtype=torch.float32, device=dev)
 
-    ops.sample(mean, sigma, free, seed, 0, pop)
-    pop[:, 0] = start
-    for g in range(G):
-        ops.score(rms, pop, t0, dt, out=block)
+    def score(g, pop, out):
+        ops.score(rms, pop, t0, dt, out=out)
         if g == 0:
-            start_dist.copy_(block[:, 0])
-        prev_idx.copy_(elite_idx)
-        elite_params, prev_params = prev_params, elite_params
-        ops.merge(block, g * M, elite_dist, elite_idx)
-        ops.update(pop, g * M, elite_dist, elite_idx, prev_idx, prev_params, elite_params, mean, sigma, free, alpha,
-                   sigma_min, sigma_max)
-        if g + 1 < G:
-            ops.sample(mean, sigma, free, seed, g + 1, pop)
-    best = elite_params[:, 0].contiguous()
-    return EnvelopeFit(params01=best, dist=elite_dist[:, 0].contiguous(), start_dist=start_dist,
+            start_dist.copy_(out[:, 0])
+    found = cross_entropy_search(start.unsqueeze(1), torch.ones(P, dtype=torch.uint8, device=dev), score, generations,
+                                 population, elites, sigma0, alpha, sigma_min, sigma_max, seed, keep_history=False, ops=ops,
+                                 what="fit_envelope")
+    best = found.params01[:, 0].contiguous()
+    return EnvelopeFit(params01=best, dist=found.dist[:, 0].contiguous(), start_dist=start_dist,
                        sounding=rms.max(dim=1).values > 0.0, units=to_units(best), rms=rms)
 
 

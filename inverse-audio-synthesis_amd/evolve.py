@@ -9,6 +9,7 @@ selection) and refits the Gaussian to them (ias_evolve_update), generation after
 Its elites are starts for ``SoundMatcher.fit``.
 """
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import torch
 
@@ -24,7 +25,7 @@ class EvolveResult:
     idx: torch.Tensor               # [N, k] int64: their global candidate indices g M + m
     mean: torch.Tensor              # [N, 78] the sampling distribution after the last generation
     sigma: torch.Tensor             # [N, 78]
-    history: torch.Tensor           # [G, N] fp32: dist[:, 0] after each generation
+    history: torch.Tensor           # [G, N] fp32: dist[:, 0] after each generation (None when not kept)
 
 
 def _check(t, dtype, shape, what):
@@ -84,18 +85,83 @@ def free_columns(frozen, device):
     return torch.tensor([(m, n) not in frozen for (m, n, *_r) in S.PARAMS], dtype=torch.uint8, device=device)
 
 
+# The three primitives of ``cross_entropy_search`` on the device.  The tests pass the same three restated in numpy on CPU
+# tensors (tests/evolve_model.py), so the loop below is one code path for both.
+DEVICE_OPS = SimpleNamespace(sample=evolve_sample, merge=topk_merge, update=evolve_update)
+
+
+@torch.no_grad()
+def cross_entropy_search(starts, free, score, generations, population, elites, sigma0, alpha, sigma_min, sigma_max, seed,
+                         keep_history=True, ops=DEVICE_OPS, what="cross_entropy_search"):
+    """The elitist cross-entropy search itself, whatever is searched -> ``EvolveResult`` (P columns in place of 78).
+
+    ``starts`` [N, S, P] fp32 in 0..1 and ``free`` [P] uint8 on the device of the search; ``score(g, pop, out)`` fills
+    out [N, M] fp32 with the distances of generation g's candidates pop [N, M, P] (the same two buffers every generation).
+    Per sound a Gaussian per column, ``mean`` (initially start 0) and ``sigma`` (initially ``sigma0``).  The first
+    population is drawn and candidates m < S of it overwritten with the starts, so a start competes as it is and can never
+    be lost.  Then per generation g: ``score``; a copy of the elite indices (``prev_idx``, taken BEFORE the merge) and a
+    swap of ``elite_params`` and ``prev_params`` (two buffers: the update gathers from one into the other);
+    ``ops.merge`` of the block at base g M into the ``elites`` best seen so far; ``ops.update``, which gathers their
+    parameters and moves the Gaussian towards them by ``alpha``, sigma kept within [sigma_min, sigma_max]; with
+    ``keep_history`` one copy of dist[:, 0] into ``history[g]``; and ``ops.sample`` for generation g + 1.  The host reads
+    nothing back and every buffer is reused.  Limits: M G <= 2^31 (the index g M + m), 1 <= k <= 64 and k <= M and
+    1 <= N <= 65535 (ias_topk_merge).  ``what`` begins every refusal."""
+    G, M, k = int(generations), int(population), int(elites)
+    if G < 1:
+        raise ValueError(f"{what}: generations must be >= 1, got {generations}")
+    if M < 1 or M > (1 << 31) // G:
+        raise ValueError(f"{what}: population must be >= 1 and population x generations at most 2^31, got {M} x {G}")
+    if not 1 <= k <= 64 or k > M:
+        raise ValueError(f"{what}: elites must be in 1..64 (ias_topk_merge) and at most the population {M}, got {k}")
+    for name, v in (("sigma0", sigma0), ("sigma_min", sigma_min), ("sigma_max", sigma_max)):
+        if not (0.0 <= float(v) < float("inf")):
+            raise ValueError(f"{what}: {name} must be finite and >= 0, got {v}")
+    if float(sigma_max) < float(sigma_min) or not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"{what}: need sigma_min <= sigma_max and alpha in [0, 1]")
+    if starts.dim() != 3 or starts.dtype != torch.float32 or not 1 <= starts.shape[1] <= M:
+        raise ValueError(f"{what}: the starts must be float32 [N, 1..{M}, P], got {starts.dtype} {tuple(starts.shape)}")
+    N, nS, P = starts.shape
+    if not 1 <= N <= 65535:
+        raise ValueError(f"{what}: 1..65535 sounds per call (ias_topk_merge), got {N}")
+    dev = starts.device
+
+    block = torch.empty((N, M), dtype=torch.float32, device=dev)
+    pop = torch.empty((N, M, P), dtype=torch.float32, device=dev)
+    mean = starts[:, 0].contiguous().clone()
+    sigma = torch.full((N, P), float(sigma0), dtype=torch.float32, device=dev)
+    elite_dist = torch.full((N, k), float("inf"), dtype=torch.float32, device=dev)
+    elite_idx = torch.full((N, k), EMPTY_INDEX, dtype=torch.int64, device=dev)
+    prev_idx = torch.empty_like(elite_idx)
+    elite_params = torch.zeros((N, k, P), dtype=torch.float32, device=dev)
+    prev_params = torch.zeros_like(elite_params)
+    history = torch.empty((G, N), dtype=torch.float32, device=dev) if keep_history else None
+
+    ops.sample(mean, sigma, free, seed, 0, pop)
+    pop[:, :nS] = starts
+    for g in range(G):
+        score(g, pop, block)
+        prev_idx.copy_(elite_idx)
+        elite_params, prev_params = prev_params, elite_params
+        ops.merge(block, g * M, elite_dist, elite_idx)
+        ops.update(pop, g * M, elite_dist, elite_idx, prev_idx, prev_params, elite_params, mean, sigma, free, alpha,
+                   sigma_min, sigma_max)
+        if keep_history:
+            history[g].copy_(elite_dist[:, 0])
+        if g + 1 < G:
+            ops.sample(mean, sigma, free, seed, g + 1, pop)
+    return EvolveResult(params01=elite_params, dist=elite_dist, idx=elite_idx, mean=mean, sigma=sigma, history=history)
+
+
 @torch.no_grad()
 def evolve_search(voice, loss, target_audio=None, target_values=None, generations=20, population=None, elites=8,
                   init_params01=None, sigma0=0.2, alpha=0.7, sigma_min=0.005, sigma_max=0.5, seed=0, frozen=()):
     """Elitist cross-entropy search of the Voice parameters nearest to each target under ``loss`` -> ``EvolveResult``.
 
     ``loss``: a ``MelSpectrogramL1`` or an ``STFTL1`` (``SoundMatcher.loss``; the multi-resolution loss is refused as by
-    ``SpectralBank``).  Give the targets as audio [N, T] or as their ``loss.target`` values.  Per sound the search keeps a
-    Gaussian per parameter, ``mean`` (initially start 0) and ``sigma`` (initially ``sigma0``), and the ``elites`` best
-    candidates seen so far.  Every generation draws ``population`` (M, a positive multiple of B = ``voice.batch_size``;
-    default 4 B) candidates clamp(mean + sigma z, 0, 1), scores them, merges them into the elites and moves the Gaussian
-    towards the elites' mean and standard deviation by ``alpha``, sigma kept within [sigma_min, sigma_max].  ``frozen``
-    ((module, name) keys as ``SoundMatcher``): those parameters stay at start 0's value in every sampled candidate.
+    ``SpectralBank``).  Give the targets as audio [N, T] or as their ``loss.target`` values.  The search and the meaning
+    of its settings are ``cross_entropy_search``'s, over the 78 parameters with ``population`` (M, a positive multiple of
+    B = ``voice.batch_size``; default 4 B) candidates per generation.  ``frozen`` ((module, name) keys as
+    ``SoundMatcher``): those parameters stay at start 0's value in every sampled candidate.
 
     ``init_params01``: None (0.5 everywhere), [N, 78] or [N, S, 78] with S <= M.  The starts are candidates m < S of
     generation 0, written over the sampled ones, so a start (a bank voice, say) competes as it is and can never be lost;
@@ -106,38 +172,22 @@ def evolve_search(voice, loss, target_audio=None, target_values=None, generation
     the same audio only at the same row (unless its noise mixer level is 0): ``dist`` is the loss of the elite rendered at
     row idx % M % B, which is not the row ``SoundMatcher.fit`` will give it (``SpectralBank`` has the same caveat).
 
-    Per generation and sound: M / B renders and value passes into one reused buffer and one ias_l1_cdist; then, for all
-    sounds at once, a copy of the elite indices, one ias_topk_merge, one ias_evolve_update, one copy into ``history`` and
-    one ias_evolve_sample for the next generation.  The host reads nothing from the device inside the loop, every buffer
-    is reused, no gradient is taken and ``voice.params01`` is left alone.  A run is a function of its arguments: the same
-    seed gives the same bits."""
+    This function is the loop's scorer: per generation and sound, M / B renders and value passes into one reused buffer
+    and one ias_l1_cdist; the loop adds, for all sounds at once, a copy of the elite indices, one ias_topk_merge, one
+    ias_evolve_update, one copy into ``history`` and one ias_evolve_sample.  No gradient is taken and ``voice.params01`` is
+    left alone.  A run is a function of its arguments: the same seed gives the same bits."""
     sc = Scorer(voice, loss)
     B, T, K, P = sc.B, sc.T, sc.K, voice.params01.shape[1]
     dev = voice.params01.device
-    G = int(generations)
-    if G < 1:
-        raise ValueError(f"evolve_search: generations must be >= 1, got {generations}")
     M = 4 * B if population is None else int(population)
     if M < 1 or M % B != 0:
         raise ValueError(f"evolve_search: population must be a positive multiple of the voice's batch size {B}, got {M}")
-    if M > (1 << 31) // G:
-        raise ValueError(f"evolve_search: population x generations must not exceed 2^31, got {M} x {G}")
-    k = int(elites)
-    if not 1 <= k <= 64 or k > M:
-        raise ValueError(f"evolve_search: elites must be in 1..64 (ias_topk_merge) and at most the population {M}, got {k}")
-    for name, v in (("sigma0", sigma0), ("sigma_min", sigma_min), ("sigma_max", sigma_max)):
-        if not (0.0 <= float(v) < float("inf")):
-            raise ValueError(f"evolve_search: {name} must be finite and >= 0, got {v}")
-    if float(sigma_max) < float(sigma_min) or not 0.0 <= float(alpha) <= 1.0:
-        raise ValueError("evolve_search: need sigma_min <= sigma_max and alpha in [0, 1]")
     if target_audio is not None:
         if target_audio.dim() != 2 or target_audio.shape[1] != T:
             raise ValueError(f"target_audio must be [N, {T}] (the voice's buffer), got {tuple(target_audio.shape)}")
         target_audio = target_audio.detach().to(device=dev, dtype=torch.float32)
     q = sc.targets(target_audio, target_values, "evolve_search")
     N = q.shape[0]
-    if N > 65535:
-        raise ValueError(f"evolve_search: at most 65535 sounds per call (ias_topk_merge), got {N}")
     if init_params01 is None:
         starts = torch.full((N, 1, P), 0.5, dtype=torch.float32, device=dev)
     else:
@@ -147,35 +197,18 @@ def evolve_search(voice, loss, target_audio=None, target_values=None, generation
             raise ValueError(f"init_params01 must be [{N}, {P}] or [{N}, starts <= {M}, {P}], got "
                              f"{tuple(init_params01.shape)}")
         starts = starts.clamp(0.0, 1.0)
-    nS = starts.shape[1]
     free = free_columns(frozen, dev)
 
-    ws = sc.workspace(1, M)
-    values = torch.empty((M, sc.F, sc.n_out), dtype=torch.float32, device=dev)
-    block = torch.empty((N, M), dtype=torch.float32, device=dev)
-    pop = torch.empty((N, M, P), dtype=torch.float32, device=dev)
-    mean = starts[:, 0].contiguous().clone()
-    sigma = torch.full((N, P), float(sigma0), dtype=torch.float32, device=dev)
-    elite_dist = torch.full((N, k), float("inf"), dtype=torch.float32, device=dev)
-    elite_idx = torch.full((N, k), EMPTY_INDEX, dtype=torch.int64, device=dev)
-    prev_idx = torch.empty_like(elite_idx)
-    elite_params = torch.zeros((N, k, P), dtype=torch.float32, device=dev)
-    prev_params = torch.zeros_like(elite_params)
-    history = torch.empty((G, N), dtype=torch.float32, device=dev)
+    own = SimpleNamespace()                              # the scorer's buffers, made once the loop has accepted the sizes
 
-    evolve_sample(mean, sigma, free, seed, 0, pop)
-    pop[:, :nS] = starts
-    sounds = pop.unbind(0)                               # views, made once: pop is rewritten in place
-    for g in range(G):
+    def score(g, pop, out):
+        if g == 0:
+            own.ws = sc.workspace(1, M)
+            own.values = torch.empty((M, sc.F, sc.n_out), dtype=torch.float32, device=dev)
+            own.sounds = pop.unbind(0)                   # views, made once: pop is rewritten in place
+        ws, values, sounds = own.ws, own.values, own.sounds
         for n in range(N):
             sc.fill(values, sounds[n])
-            l1_cdist(q[n:n + 1], values.view(M, K), out=block[n:n + 1], workspace=ws)
-        prev_idx.copy_(elite_idx)
-        elite_params, prev_params = prev_params, elite_params
-        topk_merge(block, g * M, elite_dist, elite_idx)
-        evolve_update(pop, g * M, elite_dist, elite_idx, prev_idx, prev_params, elite_params, mean, sigma, free, alpha,
-                      sigma_min, sigma_max)
-        history[g].copy_(elite_dist[:, 0])
-        if g + 1 < G:
-            evolve_sample(mean, sigma, free, seed, g + 1, pop)
-    return EvolveResult(params01=elite_params, dist=elite_dist, idx=elite_idx, mean=mean, sigma=sigma, history=history)
+            l1_cdist(q[n:n + 1], values.view(M, K), out=out[n:n + 1], workspace=ws)
+    return cross_entropy_search(starts, free, score, generations, M, elites, sigma0, alpha, sigma_min, sigma_max, seed,
+                                what="evolve_search")

@@ -344,31 +344,33 @@ def initial_starts(args, stage, target, prov):
     return bank.params01[prov.bank[1].reshape(-1)].reshape(N, -1, 78)
 
 
+def written_out(init, target):
+    """The starts as a tensor a stage can retune or reshape: ``init``, or with --init center (None) the centre matrix."""
+    import torch
+    if init is None:
+        init = torch.full((target.shape[0], 78), 0.5, dtype=torch.float32, device=target.device)
+    return init
+
+
 def pitch_stage(args, target, rate, init, prov):
     """--pitch: estimate every target's note (``prov.pitch``) and move ``keyboard.midi_f0`` of its starts onto it."""
-    import torch
     from inverse_audio_synthesis_amd.pitch import estimate_pitch, retune
     try:
         prov.pitch = estimate_pitch(target, rate, midi_lo=args.pitch_lo, midi_hi=args.pitch_hi)
     except ValueError as e:
         sys.exit(f"match_audio.py: --pitch: {e}")
-    if init is None:                                     # --init center: the centre matrix, so that it can be retuned
-        init = torch.full((target.shape[0], 78), 0.5, dtype=torch.float32, device=target.device)
-    return retune(init, prov.pitch)
+    return retune(written_out(init, target), prov.pitch)
 
 
 def envelope_stage(args, target, rate, init, prov):
     """--envelope: fit every target's envelope (``prov.envelope``) and write it into its starts."""
-    import torch
     from inverse_audio_synthesis_amd.envelope import fit_envelope, reshape
     try:
         prov.envelope = fit_envelope(target, rate, generations=args.envelope_generations,
                                      population=args.envelope_population, elites=ENVELOPE_ELITES, seed=args.seed)
     except ValueError as e:
         sys.exit(f"match_audio.py: --envelope: {e}")
-    if init is None:                                     # --init center: the centre matrix, so that it can be reshaped
-        init = torch.full((target.shape[0], 78), 0.5, dtype=torch.float32, device=target.device)
-    return reshape(init, prov.envelope)
+    return reshape(written_out(init, target), prov.envelope)
 
 
 def evolve_stage(args, stage, target, init, prov):

@@ -16,27 +16,11 @@ timed above in the same run (the bank build per batch plus ias_l1_cdist per 4,09
 voices of each of those banks.  Kernel-level figures: run it under ``rocprofv3 --kernel-trace --stats``."""
 import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import bench_common as bc
 
 VALU_PER_S = 256 * 4 * 32 * 2.4e9
-
-
-def _events_ms(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def main():
@@ -51,14 +35,12 @@ def main():
 
     import torch
     from inverse_audio_synthesis_amd import _lib
-    from inverse_audio_synthesis_amd.match import SoundMatcher
     from inverse_audio_synthesis_amd.retrieval import SpectralBank
-    from inverse_audio_synthesis_amd.voice import SynthConfig, Voice
     dev = torch.device("cuda:0")
     lib = _lib.load()
     B = 128
-    voice = Voice(SynthConfig(batch_size=B, sample_rate=44100, buffer_size_seconds=4.0, reproducible=False)).to(dev)
-    matcher = SoundMatcher(voice, loss="mel_l1", mel_kwargs=dict(n_fft=1024, hop_length=512, n_mels=128, power=2.0))
+    voice = bc.design_voice(dev)
+    matcher = bc.mel_matcher(voice)
     idx = range(args.batches)
 
     SpectralBank(voice, matcher.loss, [0])                     # first use: tables, allocations
@@ -79,8 +61,8 @@ def main():
 
         def run():
             lib.ias_l1_cdist(_lib.ptr(q), _lib.ptr(flat), N, M, K, _lib.ptr(ws), _lib.ptr(dist), _lib.stream())
-        ms = _events_ms(run, args.reps)
-        tc_ms = _events_ms(lambda: torch.cdist(q, flat, p=1.0), max(2, args.reps // 4))
+        ms = bc.event_ms(run, args.reps)[0]
+        tc_ms = bc.event_ms(lambda: torch.cdist(q, flat, p=1.0), max(2, args.reps // 4))[0]
         ref = torch.cdist(q.double(), flat.double(), p=1.0) / K
         out[f"cdist_{N}"] = {
             "shape": [N, M, K], "ias_l1_cdist_us": round(ms * 1e3, 1),
@@ -101,13 +83,13 @@ def main():
             lib.ias_topk_merge(_lib.ptr(dblock), 128, CH * B, CH * B, base[0], KS, _lib.ptr(bd), _lib.ptr(bi),
                                _lib.stream())
             base[0] += CH * B
-        out["topk_merge_128x1024_k4_us"] = round(_events_ms(merge, 50) * 1e3, 2)
+        out["topk_merge_128x1024_k4_us"] = round(bc.event_ms(merge, 50)[0] * 1e3, 2)
         qc = matcher.loss.target(voice.render(torch.rand((B, 78), generator=gen).to(dev))).reshape(B, K)
         wsc = torch.empty(lib.ias_l1_cdist_workspace_bytes(B, CH * B, K), dtype=torch.uint8, device=dev)
 
         def cdist_chunk():
             lib.ias_l1_cdist(_lib.ptr(qc), _lib.ptr(flat), B, CH * B, K, _lib.ptr(wsc), _lib.ptr(dblock), _lib.stream())
-        out["cdist_128x1024_us"] = round(_events_ms(cdist_chunk, args.reps) * 1e3, 1)
+        out["cdist_128x1024_us"] = round(bc.event_ms(cdist_chunk, args.reps)[0] * 1e3, 1)
         t0 = time.perf_counter()
         from inverse_audio_synthesis_amd.voice import sample_params01
         for i in range(256):
@@ -130,34 +112,31 @@ def main():
         out["stream"] = stream
 
     if args.quality and args.stream:
-        tgt = voice.render(torch.rand((B, 78), generator=torch.Generator().manual_seed(10_000)).to(dev))[:16]
+        tgt = bc.targets(voice)
         qs = []
         for nb in args.stream_sizes:
             d, nbi, starts = SpectralBank.search(voice, matcher.loss, range(nb), target_audio=tgt, k=4, chunk_batches=8)
-            fb = matcher.fit(tgt, init_params01=starts, steps=200)
+            fits, q = bc.fit_starts(matcher, tgt, {"bank": starts}, every="final")
             qs.append({"voices": nb * B, "nearest_distance_median": round(float(d[:, 0].median()), 4),
-                       "final": [round(float(x), 4) for x in fb.loss], "start": fb.start.tolist(),
-                       "final_median": round(float(fb.loss.median()), 4), "final_best": round(float(fb.loss.min()), 4),
-                       "final_worst": round(float(fb.loss.max()), 4)})
+                       "final": q["bank"]["final"], "start": fits["bank"].start.tolist(),
+                       "final_median": q["bank"]["median"], "final_best": q["bank"]["best"],
+                       "final_worst": q["bank"]["worst"]})
         out["quality_stream"] = qs
 
     if args.quality:
-        tgt = voice.render(torch.rand((B, 78), generator=torch.Generator().manual_seed(10_000)).to(dev))[:16]
-        steps = 200
-        center = matcher.fit(tgt, steps=steps)
-        d, nb = bank.nearest(target_audio=tgt, k=4)
-        starts = bank.params01[nb.reshape(-1)].reshape(16, 4, 78)
-        fb = matcher.fit(tgt, init_params01=starts, steps=steps)
+        tgt = bc.targets(voice)
+        d, starts = bc.nearest_starts(bank, tgt)
+        fits, q = bc.fit_starts(matcher, tgt, {"center": None, "bank": starts}, pairs=[("center", "bank")])
         out["quality"] = {
-            "targets": 16, "steps": steps, "starts": 4,
-            "center_initial": [round(float(x), 4) for x in center.initial_loss],
-            "center_final": [round(float(x), 4) for x in center.loss],
-            "bank_nearest_distance": [round(float(x), 4) for x in d[:, 0]],
-            "bank_final": [round(float(x), 4) for x in fb.loss],
-            "bank_start": fb.start.tolist(),
-            "center_final_median": round(float(center.loss.median()), 4),
-            "bank_final_median": round(float(fb.loss.median()), 4),
-            "bank_better": int((fb.loss < center.loss).sum())}
+            "targets": bc.TARGETS, "steps": bc.FIT_STEPS, "starts": bc.STARTS,
+            "center_initial": bc.rounded(fits["center"].initial_loss),
+            "center_final": q["center"]["all"],
+            "bank_nearest_distance": bc.rounded(d[:, 0]),
+            "bank_final": q["bank"]["all"],
+            "bank_start": fits["bank"].start.tolist(),
+            "center_final_median": q["center"]["median"],
+            "bank_final_median": q["bank"]["median"],
+            "bank_better": q["bank_wins"]}
     print(json.dumps(out), flush=True)
 
 

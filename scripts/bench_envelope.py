@@ -19,13 +19,10 @@ Kernel-level figures: run it under ``rocprofv3 --kernel-trace --stats``."""
 import argparse
 import json
 import os
-import statistics
-import subprocess
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import bench_common as bc
+from bench_common import ROOT
 
 HBM_BYTES_PER_S = 8e12
 FP64_LANES_PER_S = 256 * 4 * 16 * 2.4e9
@@ -33,33 +30,7 @@ FP64_PER_PAIR = 195                # fp64 vector instructions of the scorer's fr
 
 
 def _events_us(fn, reps, passes):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(passes):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b) * 1e3 / reps)
-    return {"min": round(min(out), 2), "median": round(statistics.median(out), 2), "max": round(max(out), 2)}
-
-
-def _json_line(cmd):
-    """Run a benchmark of the project in a process of its own -> the last JSON line it printed."""
-    r = subprocess.run([sys.executable] + cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=ROOT)
-    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
-    if r.returncode != 0 or not lines:
-        raise RuntimeError(f"{' '.join(cmd)} failed:\n{r.stdout[-2000:]}")
-    return json.loads(lines[-1])
-
-
-def _summary(loss):
-    return {"median": round(float(loss.median()), 4), "best": round(float(loss.min()), 4),
-            "worst": round(float(loss.max()), 4), "all": [round(float(x), 4) for x in loss]}
+    return bc.spread(bc.event_ms(fn, reps, passes), 1e3)
 
 
 def main():
@@ -72,20 +43,19 @@ def main():
 
     out = {"bench": "envelope"}
     if not args.no_headline:
-        head = _json_line([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "100", "--warmup", "5"])
+        head = bc.json_line([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "100", "--warmup", "5"])
         out["headline_step_ms"] = head["ms_per_step"]
-        out["matcher_iter_ms"] = _json_line([os.path.join(ROOT, "scripts", "bench_match.py")])["iter_ms"]
+        out["matcher_iter_ms"] = bc.json_line([os.path.join(ROOT, "scripts", "bench_match.py")])["iter_ms"]
 
     import torch
     from inverse_audio_synthesis_amd import _lib
     from inverse_audio_synthesis_amd import voice_spec as S
     from inverse_audio_synthesis_amd.envelope import envelope_score, fit_envelope, num_frames, reshape
     from inverse_audio_synthesis_amd.evolve import evolve_sample
-    from inverse_audio_synthesis_amd.voice import SynthConfig, Voice
     dev = torch.device("cuda:0")
     lib = _lib.load()
     B, rate, W, hop, M = 128, 44100, 1024, 256, 512
-    voice = Voice(SynthConfig(batch_size=B, sample_rate=rate, buffer_size_seconds=4.0, reproducible=False)).to(dev)
+    voice = bc.design_voice(dev)
     T = voice.synthconfig.buffer_size
     audio = voice.render(torch.rand((B, 78), generator=torch.Generator().manual_seed(0)).to(dev))
     F = num_frames(T, W, hop)
@@ -115,36 +85,26 @@ def main():
                 "audio_bytes": 4.0 * B * T, "audio_hbm_us": round(4.0 * B * T / HBM_BYTES_PER_S * 1e6, 2),
                 "ias_envelope_score_us": score_us, "pairs": pairs, "fp64_per_pair": FP64_PER_PAIR,
                 "score_fp64_floor_us": round(pairs * FP64_PER_PAIR / FP64_LANES_PER_S * 1e6, 2),
-                "fit_envelope_ms": {"min": round(min(fits_ms), 3), "median": round(statistics.median(fits_ms), 3),
-                                    "max": round(max(fits_ms), 3)}})
+                "fit_envelope_ms": bc.spread(fits_ms, digits=3)})
 
     if args.quality:
-        from inverse_audio_synthesis_amd.match import SoundMatcher
         from inverse_audio_synthesis_amd.retrieval import SpectralBank
-        matcher = SoundMatcher(voice, loss="mel_l1", mel_kwargs=dict(n_fft=1024, hop_length=512, n_mels=128, power=2.0))
-        tgt = voice.render(torch.rand((B, 78), generator=torch.Generator().manual_seed(10_000)).to(dev))[:16].contiguous()
+        matcher = bc.mel_matcher(voice)
+        tgt = bc.targets(voice)
         fit = fit_envelope(tgt, rate)
-        u = torch.rand((B, 78), generator=torch.Generator().manual_seed(10_000))[:16, S.INDEX[("keyboard", "duration")]]
-        steps = 200
-        centre = torch.full((16, 78), 0.5, device=dev)
-        bank = SpectralBank(voice, matcher.loss, range(32))
-        _d, nb = bank.nearest(target_audio=tgt, k=4)
-        starts = bank.params01[nb.reshape(-1)].reshape(16, 4, 78)
-        fits = {"center": matcher.fit(tgt, steps=steps).loss.cpu(),
-                "center_envelope": matcher.fit(tgt, init_params01=reshape(centre, fit), steps=steps).loss.cpu(),
-                "bank": matcher.fit(tgt, init_params01=starts, steps=steps).loss.cpu(),
-                "bank_envelope": matcher.fit(tgt, init_params01=reshape(starts, fit), steps=steps).loss.cpu()}
-        q = {"targets": 16, "steps": steps, "bank_voices": 4096, "starts": 4, "sounding": int(fit.sounding.sum()),
+        u = bc.target_params01()[:, S.INDEX[("keyboard", "duration")]]
+        centre = torch.full((bc.TARGETS, 78), 0.5, device=dev)
+        _d, starts = bc.nearest_starts(SpectralBank(voice, matcher.loss, range(bc.BANK_BATCHES)), tgt)
+        _fits, summaries = bc.fit_starts(matcher, tgt, {"center": None, "center_envelope": reshape(centre, fit),
+                                                        "bank": starts, "bank_envelope": reshape(starts, fit)},
+                                         pairs=[("center", "center_envelope"), ("bank", "bank_envelope")])
+        q = {"targets": bc.TARGETS, "steps": bc.FIT_STEPS, "bank_voices": bc.BANK_BATCHES * B, "starts": bc.STARTS,
+             "sounding": int(fit.sounding.sum()),
              "envelope_distance": [round(float(x), 5) for x in fit.dist.cpu()],
              "envelope_start_distance": [round(float(x), 5) for x in fit.start_dist.cpu()],
              "true_duration_s": [round(float(x), 3) for x in 0.01 + 3.99 * u.double() ** 2],
              "fitted_duration_s": [round(float(x), 3) for x in fit.units[:, 0].cpu()]}
-        for k, v in fits.items():
-            q[k] = _summary(v)
-        for a, b in (("center", "center_envelope"), ("bank", "bank_envelope")):
-            q[b + "_wins"] = int((fits[b] < fits[a]).sum())
-            q[b + "_losses"] = int((fits[b] > fits[a]).sum())
-        out["quality"] = q
+        out["quality"] = {**q, **summaries}
     print(json.dumps(out), flush=True)
 
 

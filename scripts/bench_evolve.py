@@ -20,32 +20,14 @@ import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-MEL = dict(n_fft=1024, hop_length=512, n_mels=128, power=2.0)
-
-
-def _events_ms(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
+import bench_common as bc
 
 
 def _setup():
     import torch
-    from inverse_audio_synthesis_amd.match import SoundMatcher
-    from inverse_audio_synthesis_amd.voice import SynthConfig, Voice
     dev = torch.device("cuda:0")
-    voice = Voice(SynthConfig(batch_size=128, sample_rate=44100, buffer_size_seconds=4.0, reproducible=False)).to(dev)
-    return dev, voice, SoundMatcher(voice, loss="mel_l1", mel_kwargs=MEL)
+    voice = bc.design_voice(dev)
+    return dev, voice, bc.mel_matcher(voice)
 
 
 def step_time(args):
@@ -65,10 +47,10 @@ def step_time(args):
     values = torch.empty((M,) + tuple(tv.shape[1:]), device=dev)
     ws = torch.empty(_lib.load().ias_l1_cdist_workspace_bytes(1, M, K), dtype=torch.uint8, device=dev)
     row = torch.empty((1, M), device=dev)
-    parts = {"render_us": _events_ms(lambda: voice.render(params, normalize=True), args.reps) * 1e3,
-             "values_us": _events_ms(lambda: values[:B].copy_(loss.target(audio)), args.reps) * 1e3,
-             "cdist_1xM_us": _events_ms(lambda: l1_cdist(tv[:1].reshape(1, K), values.view(M, K), out=row, workspace=ws),
-                                        args.reps) * 1e3}
+    parts = {"render_us": bc.event_ms(lambda: voice.render(params, normalize=True), args.reps)[0] * 1e3,
+             "values_us": bc.event_ms(lambda: values[:B].copy_(loss.target(audio)), args.reps)[0] * 1e3,
+             "cdist_1xM_us": bc.event_ms(lambda: l1_cdist(tv[:1].reshape(1, K), values.view(M, K), out=row, workspace=ws),
+                                        args.reps)[0] * 1e3}
     free = torch.ones(P, dtype=torch.uint8, device=dev)
     for N in (16, 128):
         mean, sigma = torch.rand((N, P), device=dev), torch.full((N, P), 0.2, device=dev)
@@ -85,11 +67,11 @@ def step_time(args):
         def merge():
             base[0] += M
             topk_merge(block, base[0], bd, bi)
-        p = {"sample_us": _events_ms(lambda: evolve_sample(mean, sigma, free, 0, 1, pop), 50) * 1e3,
-             "merge_us": _events_ms(merge, 50) * 1e3}
+        p = {"sample_us": bc.event_ms(lambda: evolve_sample(mean, sigma, free, 0, 1, pop), 50)[0] * 1e3,
+             "merge_us": bc.event_ms(merge, 50)[0] * 1e3}
         pi.copy_(bi)                                       # every elite is then found in prev: the gather reads pp
-        p["update_us"] = _events_ms(lambda: evolve_update(pop, base[0] + M, bd, bi, pi, pp, ep, mean, sigma, free, 0.7,
-                                                          0.005, 0.5), 50) * 1e3
+        p["update_us"] = bc.event_ms(lambda: evolve_update(pop, base[0] + M, bd, bi, pi, pp, ep, mean, sigma, free, 0.7,
+                                                          0.005, 0.5), 50)[0] * 1e3
         nb = N * (M // B)
         p["parts_sum_ms"] = (nb * (parts["render_us"] + parts["values_us"]) + N * parts["cdist_1xM_us"] + p["sample_us"]
                              + p["merge_us"] + p["update_us"]) * 1e-3
@@ -105,33 +87,29 @@ def step_time(args):
     return out
 
 
-def _summary(loss):
-    return {"final": [round(float(x), 4) for x in loss], "median": round(float(loss.median()), 4),
-            "best": round(float(loss.min()), 4), "worst": round(float(loss.max()), 4)}
-
-
 def step_quality(args):
     import torch
     from inverse_audio_synthesis_amd.evolve import evolve_search
     from inverse_audio_synthesis_amd.retrieval import SpectralBank
     dev, voice, matcher = _setup()
-    tgt = voice.render(torch.rand((128, 78), generator=torch.Generator().manual_seed(10_000)).to(dev))[:16]
-    d, idx, starts = SpectralBank.search(voice, matcher.loss, range(32), target_audio=tgt, k=4, chunk_batches=8)
-    plain = matcher.fit(tgt, init_params01=starts, steps=200)
+    tgt = bc.targets(voice)
+    d, starts = bc.nearest_starts(SpectralBank(voice, matcher.loss, range(bc.BANK_BATCHES)), tgt)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     found = evolve_search(voice, matcher.loss, target_audio=tgt, generations=args.generations, population=args.population,
                           elites=8, init_params01=starts, seed=0)
     torch.cuda.synchronize()
     search_ms = (time.perf_counter() - t0) * 1e3
-    evolved = matcher.fit(tgt, init_params01=found.params01[:, :4].contiguous(), steps=200)
-    return {"targets": 16, "steps": 200, "starts": 4, "generations": args.generations, "population": args.population,
+    _fits, q = bc.fit_starts(matcher, tgt, {"bank_adam": starts, "bank_evolve_adam": found.params01[:, :4].contiguous()},
+                             pairs=[("bank_adam", "bank_evolve_adam")], every="final")
+    return {"targets": bc.TARGETS, "steps": bc.FIT_STEPS, "starts": bc.STARTS, "generations": args.generations,
+            "population": args.population,
             "bank_nearest_distance_median": round(float(d[:, 0].median()), 4),
             "evolve_distance_median": round(float(found.dist[:, 0].median()), 4),
             "evolve_history_median": [round(float(x), 4) for x in found.history.median(dim=1).values],
             "evolve_sigma_mean": round(float(found.sigma.mean()), 4), "search_ms": round(search_ms, 1),
-            "bank_adam": _summary(plain.loss), "bank_evolve_adam": _summary(evolved.loss),
-            "evolve_better": int((evolved.loss < plain.loss).sum())}
+            "bank_adam": q["bank_adam"], "bank_evolve_adam": q["bank_evolve_adam"],
+            "evolve_better": q["bank_evolve_adam_wins"]}
 
 
 STEPS = {"time": step_time, "quality": step_quality}

@@ -13,25 +13,9 @@
 Kernel-level figures: run it under ``rocprofv3 --kernel-trace --stats``."""
 import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def _events_ms(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
+import bench_common as bc
 
 
 def _mrstft_parts(loss, audio, target, reps):
@@ -46,19 +30,19 @@ def _mrstft_parts(loss, audio, target, reps):
     tgts = loss.target(target)
     vals = [plan.values(audio, VALUE_MAG_CLAMPED, loss.eps) for plan in loss.plans]
     sums = [plan.mrstft_rows(v, t) for plan, v, t in zip(loss.plans, vals, tgts)]
-    rows_us = [_events_ms(lambda p=plan, v=v, t=t: p.mrstft_rows(v, t), reps) * 1e3
+    rows_us = [bc.event_ms(lambda p=plan, v=v, t=t: p.mrstft_rows(v, t), reps)[0] * 1e3
                for plan, v, t in zip(loss.plans, vals, tgts)]
     nbytes = sum(2 * v.numel() * 4 for v in vals)
     g = torch.ones(B, device=audio.device)
     coef = torch.empty((B, 2), dtype=torch.float64, device=audio.device)
     count = float(tgts[0][0].numel())
-    coef_us = _events_ms(lambda: lib.ias_mrstft_coef_rows(_lib.ptr(sums[0]), _lib.ptr(g), count, len(sums), B,
-                                                          _lib.ptr(coef), _lib.stream()), reps) * 1e3
+    coef_us = bc.event_ms(lambda: lib.ias_mrstft_coef_rows(_lib.ptr(sums[0]), _lib.ptr(g), count, len(sums), B,
+                                                          _lib.ptr(coef), _lib.stream()), reps)[0] * 1e3
     out = torch.empty(B, dtype=torch.float32, device=audio.device)
     ptrs = (ctypes.c_void_p * len(sums))(*[s.data_ptr() for s in sums])
     counts = (ctypes.c_double * len(sums))(*[float(t[0].numel()) for t in tgts])
-    total_us = _events_ms(lambda: lib.ias_mrstft_rows_total(ptrs, counts, len(sums), B, _lib.ptr(out), _lib.stream()),
-                          reps) * 1e3
+    total_us = bc.event_ms(lambda: lib.ias_mrstft_rows_total(ptrs, counts, len(sums), B, _lib.ptr(out), _lib.stream()),
+                          reps)[0] * 1e3
     return {"mrstft_rows_us": round(sum(rows_us), 2), "mrstft_rows_us_per_resolution": [round(u, 2) for u in rows_us],
             "mrstft_rows_bytes": nbytes, "mrstft_rows_hbm_floor_us": round(nbytes / 8e12 * 1e6, 2),
             "mrstft_coef_rows_us": round(coef_us, 2), "mrstft_rows_total_us": round(total_us, 2)}
@@ -85,7 +69,7 @@ def main():
     gen = torch.Generator().manual_seed(0)
     target = voice.render(torch.rand((B, 78), generator=gen).to(dev))
     init = torch.rand((B, 78), generator=gen).to(dev)
-    matcher = SoundMatcher(voice, loss=args.loss, mel_kwargs=dict(n_fft=1024, hop_length=512, n_mels=128, power=2.0),
+    matcher = SoundMatcher(voice, loss=args.loss, mel_kwargs=bc.MEL,
                            stft_kwargs=dict(n_fft=1024, hop_length=512, power=1.0), lr=0.01)
 
     def fit_s(steps):
@@ -107,7 +91,7 @@ def main():
         plan = matcher.loss.mel.plan if args.loss == "mel_l1" else matcher.loss.plan
         vals = plan.values(voice.render(init), matcher.loss.mel.value_mode if args.loss == "mel_l1" else matcher.loss.value_mode)
         tgt = matcher.loss.target(target)
-        l1_ms = _events_ms(lambda: plan.l1_rows(vals, tgt), args.reps)
+        l1_ms = bc.event_ms(lambda: plan.l1_rows(vals, tgt), args.reps)[0]
         floor_us = 2 * vals.numel() * 4 / 8e12 * 1e6
         rows = {"l1_rows_us": round(l1_ms * 1e3, 2), "l1_rows_bytes": 2 * vals.numel() * 4,
                 "l1_rows_hbm_floor_us": round(floor_us, 2)}
@@ -123,8 +107,8 @@ def main():
     loss = torch.ones(B, device=dev)
     free = torch.ones(78, dtype=torch.uint8, device=dev)
     active = torch.ones(B, dtype=torch.uint8, device=dev)
-    adam_ms = _events_ms(lambda: match_adam_step(p, grad, m, v, step, loss, best_loss, best_params, free, active, skipped,
-                                                 1e-4, (0.9, 0.999), 1e-8), args.reps)
+    adam_ms = bc.event_ms(lambda: match_adam_step(p, grad, m, v, step, loss, best_loss, best_params, free, active, skipped,
+                                                 1e-4, (0.9, 0.999), 1e-8), args.reps)[0]
     out = {"workload": "match", "loss": args.loss, "batch": B, "T": voice.synthconfig.buffer_size, "steps": args.steps,
            "iter_ms": round(iter_ms, 4), **rows, "adam_step_us": round(adam_ms * 1e3, 2),
            "final_over_initial_median": round(float((res.loss / res.initial_loss).median()), 4),

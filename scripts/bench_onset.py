@@ -13,30 +13,14 @@ The audio is white noise: none of the four kernels' times depends on the values,
 Kernel-level figures: run it under ``rocprofv3 --kernel-trace --stats``."""
 import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import bench_common as bc
 
 HBM_BYTES_PER_S = 8e12
 
 
 def _events_us(fn, reps, passes):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(passes):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b) * 1e3 / reps)
-    return {"min": round(min(out), 2), "median": round(statistics.median(out), 2), "max": round(max(out), 2)}
+    return bc.spread(bc.event_ms(fn, reps, passes), 1e3)
 
 
 def _shape(B, L, rate, reps, passes):

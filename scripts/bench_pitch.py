@@ -14,31 +14,10 @@ targets' true sounding pitch (``keyboard.midi_f0`` plus the tuning of the louder
 Kernel-level figures: run it under ``rocprofv3 --kernel-trace --stats``."""
 import argparse
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import bench_common as bc
 
 VALU_PER_S = 256 * 4 * 32 * 2.4e9
-
-
-def _events_ms(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
-
-
-def _summary(loss):
-    return {"median": round(float(loss.median()), 4), "best": round(float(loss.min()), 4),
-            "worst": round(float(loss.max()), 4), "all": [round(float(x), 4) for x in loss]}
 
 
 def main():
@@ -51,11 +30,10 @@ def main():
     from inverse_audio_synthesis_amd import _lib
     from inverse_audio_synthesis_amd import voice_spec as S
     from inverse_audio_synthesis_amd.pitch import estimate_pitch, num_frames, retune, yin_plan
-    from inverse_audio_synthesis_amd.voice import SynthConfig, Voice
     dev = torch.device("cuda:0")
     lib = _lib.load()
     B, rate, hop, thr = 128, 44100, 512, 0.15
-    voice = Voice(SynthConfig(batch_size=B, sample_rate=rate, buffer_size_seconds=4.0, reproducible=False)).to(dev)
+    voice = bc.design_voice(dev)
     T = voice.synthconfig.buffer_size
     audio = voice.render(torch.rand((B, 78), generator=torch.Generator().manual_seed(0)).to(dev))
     W, tau_min, tau_max = yin_plan(rate)
@@ -66,48 +44,38 @@ def main():
     def run():
         lib.ias_pitch_yin(_lib.ptr(audio), B, T, W, tau_min, tau_max, hop, thr, _lib.ptr(period), _lib.ptr(aper),
                           _lib.ptr(energy), None, _lib.stream())
-    ms = _events_ms(run, args.reps)
+    ms = bc.event_ms(run, args.reps)[0]
     pairs = float(B) * F * W * tau_max
     out = {"bench": "pitch", "shape": [B, T], "W": W, "tau_min": tau_min, "tau_max": tau_max, "hop": hop, "frames": F,
            "pairs": pairs, "ias_pitch_yin_ms": round(ms, 3), "compute_floor_ms": round(2.0 * pairs / VALU_PER_S * 1e3, 3),
-           "estimate_pitch_ms": round(_events_ms(lambda: estimate_pitch(audio, rate), max(2, args.reps // 4)), 3),
+           "estimate_pitch_ms": round(bc.event_ms(lambda: estimate_pitch(audio, rate), max(2, args.reps // 4))[0], 3),
            "device": torch.cuda.get_device_name(dev)}
     out["floor_fraction"] = round(out["compute_floor_ms"] / out["ias_pitch_yin_ms"], 3)
 
     if args.quality:
-        from inverse_audio_synthesis_amd.match import SoundMatcher
         from inverse_audio_synthesis_amd.retrieval import SpectralBank
-        matcher = SoundMatcher(voice, loss="mel_l1", mel_kwargs=dict(n_fft=1024, hop_length=512, n_mels=128, power=2.0))
-        truth01 = torch.rand((B, 78), generator=torch.Generator().manual_seed(10_000))[:16]
-        tgt = voice.render(torch.rand((B, 78), generator=torch.Generator().manual_seed(10_000)).to(dev))[:16].contiguous()
+        matcher = bc.mel_matcher(voice)
+        truth01, tgt = bc.target_params01(), bc.targets(voice)
         est = estimate_pitch(tgt, rate)
         second = truth01[:, S.INDEX[("mixer", "vco_2")]] > truth01[:, S.INDEX[("mixer", "vco_1")]]
         tuning01 = torch.where(second, truth01[:, S.INDEX[("vco_2", "tuning")]], truth01[:, S.INDEX[("vco_1", "tuning")]])
         true_midi = 127.0 * truth01[:, S.INDEX[("keyboard", "midi_f0")]] + (-24.0 + 48.0 * tuning01)
         voiced = est.voiced.cpu()
         err = (est.midi.cpu() - true_midi)[voiced].abs()
-        steps = 200
-        centre = torch.full((16, 78), 0.5, device=dev)
-        bank = SpectralBank(voice, matcher.loss, range(32))
-        _d, nb = bank.nearest(target_audio=tgt, k=4)
-        starts = bank.params01[nb.reshape(-1)].reshape(16, 4, 78)
-        fits = {"center": matcher.fit(tgt, steps=steps).loss.cpu(),
-                "center_pitch": matcher.fit(tgt, init_params01=retune(centre, est), steps=steps).loss.cpu(),
-                "bank": matcher.fit(tgt, init_params01=starts, steps=steps).loss.cpu(),
-                "bank_pitch": matcher.fit(tgt, init_params01=retune(starts, est), steps=steps).loss.cpu()}
-        q = {"targets": 16, "steps": steps, "bank_voices": 4096, "starts": 4, "voiced": int(voiced.sum()),
+        centre = torch.full((bc.TARGETS, 78), 0.5, device=dev)
+        _d, starts = bc.nearest_starts(SpectralBank(voice, matcher.loss, range(bc.BANK_BATCHES)), tgt)
+        _fits, summaries = bc.fit_starts(matcher, tgt, {"center": None, "center_pitch": retune(centre, est), "bank": starts,
+                                                        "bank_pitch": retune(starts, est)},
+                                         pairs=[("center", "center_pitch"), ("bank", "bank_pitch")])
+        q = {"targets": bc.TARGETS, "steps": bc.FIT_STEPS, "bank_voices": bc.BANK_BATCHES * B, "starts": bc.STARTS,
+             "voiced": int(voiced.sum()),
              "true_midi": [round(float(x), 2) for x in true_midi],
              "estimated_midi": [round(float(x), 2) if v else None for x, v in zip(est.midi.cpu(), voiced)],
              "confidence": [round(float(x), 3) for x in est.confidence.cpu()],
              "estimate_abs_error_median": round(float(err.median()), 3) if len(err) else None,
              "estimate_abs_error_max": round(float(err.max()), 3) if len(err) else None,
              "estimate_within_half_semitone": int((err <= 0.5).sum())}
-        for k, v in fits.items():
-            q[k] = _summary(v)
-        for a, b in (("center", "center_pitch"), ("bank", "bank_pitch")):
-            q[b + "_wins"] = int((fits[b] < fits[a]).sum())
-            q[b + "_losses"] = int((fits[b] > fits[a]).sum())
-        out["quality"] = q
+        out["quality"] = {**q, **summaries}
     print(json.dumps(out), flush=True)
 
 

@@ -11,27 +11,11 @@ torch ops on the GPU (the F.pad + F.conv1d(stride=o) form torchaudio uses, with 
 difference between the two.  Kernel-level figures: run it under ``rocprofv3 --kernel-trace --stats``."""
 import argparse
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import bench_common as bc
 
 FMA_PER_S = 256 * 4 * 32 * 2.4e9
 HBM_BYTES_PER_S = 8e12
-
-
-def _events_ms(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def main():
@@ -62,14 +46,14 @@ def main():
             lib.ias_resample(_lib.ptr(x), _lib.ptr(taps_d), _lib.ptr(y), B, T, o, n, width, K, _lib.stream())
         _lib.check(lib.ias_resample(_lib.ptr(x), _lib.ptr(taps_d), _lib.ptr(y), B, T, o, n, width, K, _lib.stream()),
                    "ias_resample")
-        ms = _events_ms(run, args.reps)
+        ms = bc.event_ms(run, args.reps)[0]
         w = taps_d[:, None, :]
 
         def conv():
             r = F.conv1d(F.pad(x[:, None], (width, width + o)), w, stride=o)
             return r.transpose(1, 2).reshape(B, -1)[:, :T_out]
         with torch.no_grad():
-            conv_ms = _events_ms(conv, max(2, args.reps // 5))
+            conv_ms = bc.event_ms(conv, max(2, args.reps // 5))[0]
             diff = float((conv() - y).abs().max())
         out[f"{orig}_{new}"] = {
             "o_n_K": [o, n, K], "T_in": T, "T_out": T_out, "ias_resample_us": round(ms * 1e3, 1),

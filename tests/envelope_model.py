@@ -1,6 +1,6 @@
 """The envelope stage restated from the text of its contracts (include/ias_hip.h: ias_envelope_frames, ias_envelope_score;
-envelope.reshape) in fp64 numpy, and the five primitives of ``envelope.fit_envelope`` on CPU tensors, the search's own from
-tests/evolve_model.py.  Test support: no test lives here."""
+envelope.reshape) in fp64 numpy, and the five primitives of ``envelope.fit_envelope`` on CPU tensors, the search's own
+three from tests/evolve_model.py.  Test support: no test lives here."""
 import math
 from types import SimpleNamespace
 
@@ -84,21 +84,6 @@ def score(env, cand, t0, dt):
     return out.astype(np.float32)
 
 
-def merge(dist, base, best_dist, best_idx):
-    """ias_topk_merge on arrays: -> (best_dist, best_idx) [N, k] after merging the block."""
-    dist, best_dist, best_idx = np.asarray(dist), np.asarray(best_dist), np.asarray(best_idx)
-    N, M = dist.shape
-    k = best_dist.shape[1]
-    d = np.concatenate([best_dist, dist], axis=1)
-    ix = np.concatenate([best_idx, np.broadcast_to(base + np.arange(M, dtype=np.int64), (N, M))], axis=1)
-    key = np.where(np.isfinite(d), d, np.inf)
-    od, oi = np.empty_like(best_dist), np.empty_like(best_idx)
-    for n in range(N):
-        order = np.lexsort((ix[n], key[n]))[:k]
-        od[n], oi[n] = d[n, order], ix[n, order]
-    return od, oi
-
-
 def reshape(params01, fit01, sounding):
     """params01 [N, 78] or [N, S, 78], fit01 [N, 6], sounding [N] -> the reshaped copy (numpy, the input's dtype)."""
     from inverse_audio_synthesis_amd import voice_spec as S
@@ -157,30 +142,9 @@ def _frames_op(audio, W, hop):
     return torch.from_numpy(frames(audio.numpy(), int(W), int(hop)))
 
 
-def _sample_op(mean, sigma, free, seed, generation, out):
-    pop = em.sample(mean.numpy(), sigma.numpy(), free.numpy(), out.shape[1], seed=seed, generation=generation)
-    out.copy_(torch.from_numpy(pop.astype(np.float32)))
-    return out
-
-
 def _score_op(env, cand, t0, dt, out):
     out.copy_(torch.from_numpy(score(env.numpy(), cand.numpy(), t0, dt)))
     return out
 
 
-def _merge_op(dist, base, best_dist, best_idx):
-    d, i = merge(dist.numpy(), base, best_dist.numpy(), best_idx.numpy())
-    best_dist.copy_(torch.from_numpy(d))
-    best_idx.copy_(torch.from_numpy(i))
-
-
-def _update_op(pop, base, elite_dist, elite_idx, prev_idx, prev_params, elite_params, mean, sigma, free, alpha, sigma_min,
-               sigma_max):
-    ep, m, s = em.update(pop.numpy(), base, elite_dist.numpy(), elite_idx.numpy(), prev_idx.numpy(), prev_params.numpy(),
-                         mean.numpy(), sigma.numpy(), free.numpy(), alpha, sigma_min, sigma_max)
-    elite_params.copy_(torch.from_numpy(ep))
-    mean.copy_(torch.from_numpy(m))
-    sigma.copy_(torch.from_numpy(s))
-
-
-MODEL_OPS = SimpleNamespace(frames=_frames_op, sample=_sample_op, score=_score_op, merge=_merge_op, update=_update_op)
+MODEL_OPS = SimpleNamespace(frames=_frames_op, score=_score_op, **vars(em.MODEL_OPS))

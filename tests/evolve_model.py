@@ -1,6 +1,10 @@
-"""The evolutionary search's device primitives restated in numpy (fp64): Philox4x32-10, the sampler (ias_evolve_sample) and
-the distribution update (ias_evolve_update), as include/ias_hip.h specifies them.  Test support: no test lives here."""
+"""The evolutionary search's device primitives restated in numpy (fp64): Philox4x32-10, the sampler (ias_evolve_sample),
+the running top-k (ias_topk_merge) and the distribution update (ias_evolve_update), as include/ias_hip.h specifies them,
+and the three as ``evolve.cross_entropy_search``'s ``ops`` on CPU tensors.  Test support: no test lives here."""
+from types import SimpleNamespace
+
 import numpy as np
+import torch
 
 M0, M1 = 0xD2511F53, 0xCD9E8D57
 W0, W1 = 0x9E3779B9, 0xBB67AE85
@@ -55,6 +59,21 @@ def sample(mean, sigma, free, M, n_base=0, m_base=0, seed=0, generation=0):
     return np.where(np.asarray(free, dtype=bool)[None, None, :], out, mean[:, None, :])
 
 
+def merge(dist, base, best_dist, best_idx):
+    """ias_topk_merge on arrays: -> (best_dist, best_idx) [N, k] after merging the block."""
+    dist, best_dist, best_idx = np.asarray(dist), np.asarray(best_dist), np.asarray(best_idx)
+    N, M = dist.shape
+    k = best_dist.shape[1]
+    d = np.concatenate([best_dist, dist], axis=1)
+    ix = np.concatenate([best_idx, np.broadcast_to(base + np.arange(M, dtype=np.int64), (N, M))], axis=1)
+    key = np.where(np.isfinite(d), d, np.inf)
+    od, oi = np.empty_like(best_dist), np.empty_like(best_idx)
+    for n in range(N):
+        order = np.lexsort((ix[n], key[n]))[:k]
+        od[n], oi[n] = d[n, order], ix[n, order]
+    return od, oi
+
+
 def update(pop, base, elite_dist, elite_idx, prev_idx, prev_params, mean, sigma, free, alpha, sigma_min, sigma_max):
     """-> (elite_params [N, k, P] fp32, mean [N, P] fp32, sigma [N, P] fp32) as ias_evolve_update leaves them."""
     pop, prev_params = np.asarray(pop, dtype=np.float32), np.asarray(prev_params, dtype=np.float32)
@@ -95,3 +114,28 @@ def update(pop, base, elite_dist, elite_idx, prev_idx, prev_params, mean, sigma,
                 s2 = np.minimum(sigma_max, np.maximum(sigma_min, (1.0 - alpha) * float(sigma[n, j]) + alpha * np.sqrt(v)))
             mean[n, j], sigma[n, j] = np.float32(m2), np.float32(s2)
     return ep, mean, sigma
+
+
+# ------------------------------------------------------------------ the primitives of the search loop on CPU tensors
+def _sample_op(mean, sigma, free, seed, generation, out):
+    pop = sample(mean.numpy(), sigma.numpy(), free.numpy(), out.shape[1], seed=seed, generation=generation)
+    out.copy_(torch.from_numpy(pop.astype(np.float32)))
+    return out
+
+
+def _merge_op(dist, base, best_dist, best_idx):
+    d, i = merge(dist.numpy(), base, best_dist.numpy(), best_idx.numpy())
+    best_dist.copy_(torch.from_numpy(d))
+    best_idx.copy_(torch.from_numpy(i))
+
+
+def _update_op(pop, base, elite_dist, elite_idx, prev_idx, prev_params, elite_params, mean, sigma, free, alpha, sigma_min,
+               sigma_max):
+    ep, m, s = update(pop.numpy(), base, elite_dist.numpy(), elite_idx.numpy(), prev_idx.numpy(), prev_params.numpy(),
+                      mean.numpy(), sigma.numpy(), free.numpy(), alpha, sigma_min, sigma_max)
+    elite_params.copy_(torch.from_numpy(ep))
+    mean.copy_(torch.from_numpy(m))
+    sigma.copy_(torch.from_numpy(s))
+
+
+MODEL_OPS = SimpleNamespace(sample=_sample_op, merge=_merge_op, update=_update_op)

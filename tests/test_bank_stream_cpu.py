@@ -1,5 +1,6 @@
 """Streamed spectral bank search without a GPU: match_audio.py's --bank-stream flag, the declared entry point, its host-side
-refusals, and the merge order restated in torch (the reference tests/test_bank_stream_gpu.py leans on)."""
+refusals, and the merge order restated in numpy (tests/evolve_model.py; the reference tests/test_bank_stream_gpu.py leans
+on)."""
 import math
 import os
 import re
@@ -8,6 +9,8 @@ import pytest
 import torch
 
 from conftest import ROOT
+
+import evolve_model as em
 
 INT64_MAX = torch.iinfo(torch.int64).max
 
@@ -52,20 +55,11 @@ def test_topk_merge_refuses_before_touching_the_device(lib):
     assert call(N=65536) == -2
 
 
-def _merge(state, block, base, k):
-    """The order ias_topk_merge implements, restated: the candidates are the running entries and the block's, ranked by
-    ``rank_distances`` over the distances with ties resolved by GLOBAL index (the concatenation is put in index order
-    first, so the stable sort's position order is the index order; empty slots, index INT64_MAX, go last), cut to k."""
-    from inverse_audio_synthesis_amd.retrieval import rank_distances
-    sd, si = state
-    N, M = block.shape
-    d = torch.cat([sd, block], 1)
-    i = torch.cat([si, (base + torch.arange(M)).expand(N, M)], 1)
-    by_index = torch.sort(i, dim=1, stable=True).indices
-    d, i = torch.gather(d, 1, by_index), torch.gather(i, 1, by_index)
-    d = torch.where(i == INT64_MAX, torch.full_like(d, math.inf), d)
-    order = rank_distances(d)[:, :k]
-    return torch.gather(d, 1, order), torch.gather(i, 1, order)
+def _merge(state, block, base):
+    """ias_topk_merge as tests/evolve_model.py restates it (the model the search loop's CPU tests run on), on torch tensors:
+    the running entries and the block's, ranked by ``rank_distances``' key with ties by GLOBAL index, cut to k."""
+    d, i = em.merge(block.numpy(), base, state[0].numpy(), state[1].numpy())
+    return torch.from_numpy(d), torch.from_numpy(i)
 
 
 def _fresh(N, k):
@@ -90,12 +84,12 @@ def test_restated_merge_is_associative_and_equals_the_full_sort(k):
         state = _fresh(N, k)
         for j in order:
             a, b = cuts[j]
-            state = _merge(state, d[:, a:b], a, k)
+            state = _merge(state, d[:, a:b], a)
         results.append(state)
-    results.append(_merge(_fresh(N, k), d, 0, k))
+    results.append(_merge(_fresh(N, k), d, 0))
     # (A + B) + C == A + (B + C): merging a merged state of two blocks (as a block list would be) changes nothing
-    left = _merge(_merge(_merge(_fresh(N, k), d[:, :100], 0, k), d[:, 100:200], 100, k), d[:, 200:], 200, k)
-    right = _merge(_merge(_merge(_fresh(N, k), d[:, 200:], 200, k), d[:, 100:200], 100, k), d[:, :100], 0, k)
+    left = _merge(_merge(_merge(_fresh(N, k), d[:, :100], 0), d[:, 100:200], 100), d[:, 200:], 200)
+    right = _merge(_merge(_merge(_fresh(N, k), d[:, 200:], 200), d[:, 100:200], 100), d[:, :100], 0)
     results += [left, right]
     for sd, si in results:
         assert torch.equal(si, want_idx)
@@ -104,6 +98,6 @@ def test_restated_merge_is_associative_and_equals_the_full_sort(k):
 
 def test_restated_merge_keeps_empty_slots_when_candidates_run_out():
     d = torch.tensor([[1.0, math.nan, 1.0]])
-    sd, si = _merge(_merge(_fresh(1, 5), d[:, 2:], 2, 5), d[:, :2], 0, 5)
+    sd, si = _merge(_merge(_fresh(1, 5), d[:, 2:], 2), d[:, :2], 0)
     assert si.tolist() == [[0, 2, 1, INT64_MAX, INT64_MAX]]
     assert sd[0, :2].tolist() == [1.0, 1.0] and math.isnan(sd[0, 2]) and sd[0, 3:].tolist() == [math.inf, math.inf]

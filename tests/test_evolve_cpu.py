@@ -1,9 +1,11 @@
 """Evolutionary search stage without a GPU: the restated Philox4x32-10 against the Random123 known-answer vectors, the
-declared entry points, their host-side refusals, match_audio.py's --evolve flags and evolve_search's own refusals."""
+declared entry points, their host-side refusals, match_audio.py's --evolve flags, evolve_search's own refusals, and the
+search loop itself (``evolve.cross_entropy_search``) run on the numpy primitives of tests/evolve_model.py."""
 import ctypes
 import math
 import os
 import re
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -151,3 +153,119 @@ def test_search_refuses_bad_sizes():
         evolve_search(v, loss, target_audio=torch.zeros(1, 16000), target_values=tv)
     with pytest.raises(KeyError):
         evolve_search(v, loss, target_values=tv, frozen=[("mixer", "nothing")])
+
+
+# ------------------------------------------------------------------------------------------------ the search loop
+N, P, M, K, G = 3, 6, 16, 4, 5
+HIDDEN = torch.rand((N, P), generator=torch.Generator().manual_seed(40))
+SETTINGS = dict(generations=G, population=M, elites=K, sigma0=0.2, alpha=0.7, sigma_min=0.005, sigma_max=0.5)
+FIELDS = ("params01", "dist", "idx", "mean", "sigma")
+
+
+def _score(g, pop, out):
+    """Mean |candidate - hidden vector| per sound, in fp64 numpy."""
+    d = np.abs(pop.numpy().astype(np.float64) - HIDDEN.numpy().astype(np.float64)[:, None]).mean(-1)
+    out.copy_(torch.from_numpy(d.astype(np.float32)))
+
+
+def _starts(S=1, seed=41):
+    return torch.rand((N, S, P), generator=torch.Generator().manual_seed(seed))
+
+
+def _search(starts=None, free=None, score=_score, seed=3, **kw):
+    from inverse_audio_synthesis_amd.evolve import cross_entropy_search
+    starts = _starts() if starts is None else starts
+    free = torch.ones(starts.shape[2], dtype=torch.uint8) if free is None else free
+    return cross_entropy_search(starts, free, score, seed=seed, **{"ops": em.MODEL_OPS, "what": "a_search", **SETTINGS, **kw})
+
+
+def test_loop_is_a_function_of_its_seed():
+    a, b, c = _search(), _search(), _search(seed=4)
+    for f in FIELDS + ("history",):
+        assert torch.equal(getattr(a, f), getattr(b, f)), f
+    assert not torch.equal(a.params01, c.params01) and not torch.equal(a.idx, c.idx)
+    assert a.params01.shape == (N, K, P) and a.dist.shape == a.idx.shape == (N, K) and a.idx.dtype == torch.int64
+    assert a.mean.shape == a.sigma.shape == (N, P) and ((a.idx >= 0) & (a.idx < G * M)).all()
+
+
+def test_loop_history_falls_and_ends_at_the_best_elite():
+    a = _search()
+    assert a.history.shape == (G, N)
+    assert (a.history[1:] <= a.history[:-1]).all() and (a.history[-1] < a.history[0]).any()
+    assert torch.equal(a.history[-1], a.dist[:, 0])
+    assert (a.dist[:, 1:] >= a.dist[:, :-1]).all()
+    # every elite's distance is the scorer's value of its parameters
+    again = torch.empty((N, K))
+    _score(0, a.params01, again)
+    assert torch.equal(again, a.dist)
+
+
+def test_loop_without_history_differs_in_nothing_else():
+    a, b = _search(), _search(keep_history=False)
+    assert b.history is None
+    for f in FIELDS:
+        assert torch.equal(getattr(a, f), getattr(b, f)), f
+
+
+def test_loop_keeps_a_planted_start():
+    starts = _starts(S=2)
+    starts[:, 1] = HIDDEN
+    r = _search(starts=starts)
+    assert r.dist[:, 0].tolist() == [0.0] * N and r.idx[:, 0].tolist() == [1] * N
+    assert torch.equal(r.params01[:, 0], HIDDEN)
+    assert (r.history == 0.0).all()
+
+
+def test_loop_leaves_frozen_columns_at_start_0():
+    starts, free = _starts(), torch.ones(P, dtype=torch.uint8)
+    free[1] = free[4] = 0
+    r = _search(starts=starts, free=free)
+    assert torch.equal(r.params01[:, :, [1, 4]], starts[:, :1, [1, 4]].expand(N, K, 2))
+    assert torch.equal(r.mean[:, [1, 4]], starts[:, 0, [1, 4]])
+    assert not torch.equal(r.mean[:, [0, 2, 3, 5]], starts[:, 0, [0, 2, 3, 5]])
+
+
+def _counting(ops):
+    """``ops`` with every primitive counted -> (the counting ops, the counts by name)."""
+    calls = {name: 0 for name in vars(ops)}
+
+    def counted(name, fn):
+        def call(*a, **kw):
+            calls[name] += 1
+            return fn(*a, **kw)
+        return call
+    return SimpleNamespace(**{name: counted(name, fn) for name, fn in vars(ops).items()}), calls
+
+
+def test_loop_calls_every_primitive_once_per_generation():
+    ops, calls = _counting(em.MODEL_OPS)
+    seen = []
+
+    def score(g, pop, out):
+        seen.append(g)
+        assert tuple(pop.shape) == (N, M, P) and tuple(out.shape) == (N, M)
+        _score(g, pop, out)
+    _search(score=score, ops=ops)
+    assert seen == list(range(G))
+    assert calls == {"sample": G, "merge": G, "update": G}
+
+
+def test_fit_envelope_calls_the_loop_once():
+    import envelope_model as vm
+    from inverse_audio_synthesis_amd.envelope import fit_envelope
+    ops, calls = _counting(vm.MODEL_OPS)
+    audio = torch.zeros((2, 2000), dtype=torch.float32)
+    audio[:, 100:900] = 0.25
+    fit_envelope(audio, 8000, W=256, hop=64, generations=3, population=16, elites=4, ops=ops)
+    assert calls == {"frames": 1, "score": 3, "sample": 3, "merge": 3, "update": 3}
+
+
+@pytest.mark.parametrize("kw", [dict(generations=0), dict(population=0), dict(elites=0), dict(elites=65, population=128),
+                                dict(elites=M + 1), dict(sigma0=float("inf")), dict(sigma0=float("nan")),
+                                dict(sigma_min=0.6, sigma_max=0.5), dict(alpha=1.5), dict(starts=torch.zeros((0, 1, P)))],
+                         ids=lambda kw: "-".join(kw))
+def test_loop_refusals_name_the_caller(kw):
+    def never(g, pop, out):
+        raise AssertionError("scored after a refusal")
+    with pytest.raises(ValueError, match="^a_search: "):
+        _search(score=never, **kw)
