@@ -636,12 +636,12 @@ int ias_dwconv_forward(const float* x, const float* w, float* out, int B, int C,
 int ias_dwconv_backward_data(const float* g, const float* w, float* gx, int B, int C, int H, int W, int K, int S,
                              void* stream);
 long long ias_dwconv_weight_scratch_hw(int B, int C, int H, int W, int K, int S);   /* floats, for this plane size */
+/* The weight-gradient entries here and below (ias_dwconv_, ias_pwconv_, ias_stem_backward_weight, ias_colsum) share one
+ * convention: they leave per-workgroup partial rows in `scratch` and return their number (> 0) or a negative IAS_ERR_*.
+ * With gw (ias_colsum: out) non-NULL they also run their reduction launch; with NULL the rows stay for
+ * ias_reduce_partials_multi below.  Rows here: C K K floats each. */
 int ias_dwconv_backward_weight(const float* x, const float* g, float* gw, float* scratch, int B, int C, int H, int W,
                                int K, int S, void* stream);
-/* ... without its reduction launch: the partial rows stay in `scratch` -> their number (> 0; C K K floats each) for
- * ias_reduce_partials_multi below, or a negative IAS_ERR_* */
-int ias_dwconv_backward_weight_partials(const float* x, const float* g, float* scratch, int B, int C, int H, int W, int K,
-                                        int S, void* stream);
 /* Conv2d(3, 16, 3, stride 2, padding 1, bias=False): x [B,3,H,W], w [16,3,3,3] -> out [B,16,Ho,Wo]; weight gradient. */
 /* 1x1 convolutions (nn.Conv2d(Cin, Cout, 1, bias=False)) of torchvision's mobilenet_v3_small.features as run at
  * /root/reference/audioembed.py:61, NCHW fp32, on fp32 MFMA: x [B,Cin,HW], w [Cout,Cin], y / g [B,Cout,HW].
@@ -649,32 +649,25 @@ int ias_dwconv_backward_weight_partials(const float* x, const float* g, float* s
  * 16-padded Cin * Cout <= 16384, Cin <= 240); the other entry points return IAS_ERR_UNSUPPORTED otherwise.
  * The weight gradient is reduced in a fixed order (deterministic); scratch: ias_pwconv_weight_scratch floats. */
 int ias_pwconv_supported(int Cin, int Cout);
-int ias_pwconv_forward(const float* x, const float* w, float* y, int B, int Cin, int Cout, int HW, void* stream);
-int ias_pwconv_backward_data(const float* g, const float* w, float* gx, int B, int Cin, int Cout, int HW, void* stream);
-long long ias_pwconv_weight_scratch(int B, int Cin, int Cout, int HW);
-int ias_pwconv_backward_weight(const float* g, const float* x, float* gw, float* scratch, int B, int Cin, int Cout, int HW,
-                               void* stream);
-/* ... without its reduction launch -> the number of partial rows (> 0; Cout Cin floats each), or a negative IAS_ERR_* */
-int ias_pwconv_backward_weight_partials(const float* g, const float* x, float* scratch, int B, int Cin, int Cout, int HW,
-                                        void* stream);
-/* The projection behind a squeeze-excitation block with the block's gate taken on load: y[b] = W (x[b] * scale[b]),
- * scale [B,Cin] -- torchvision InvertedResidual's `SqueezeExcitation -> Conv2dNormActivation(cexp, cout, 1)` inside
- * mobilenet_v3_small.features (run at /root/reference/audioembed.py:61) without the gate's own pass over the expanded map
+/* scale (or NULL): the projection behind a squeeze-excitation block with the block's gate taken on load:
+ * y[b] = W (x[b] * scale[b]), scale [B,Cin] -- torchvision InvertedResidual's
+ * `SqueezeExcitation -> Conv2dNormActivation(cexp, cout, 1)` inside mobilenet_v3_small.features (run at /root/reference/audioembed.py:61) without the gate's own pass over the expanded map
  * (`scale * input` of torchvision's SqueezeExcitation.forward); same bits as ias_se_scale followed by ias_pwconv_forward.
  * The input gradient of the product x * scale is ias_pwconv_backward_data; the weight gradient is
- * gw = sum_b g[b] (x[b] * scale[b])^T (scale applied once per sample and column where the sums leave the accumulators). */
-int ias_pwconv_forward_scaled(const float* x, const float* scale, const float* w, float* y, int B, int Cin, int Cout, int HW,
-                              void* stream);
-int ias_pwconv_backward_weight_scaled(const float* g, const float* x, const float* scale, float* gw, float* scratch, int B,
-                                      int Cin, int Cout, int HW, void* stream);
-int ias_pwconv_backward_weight_partials_scaled(const float* g, const float* x, const float* scale, float* scratch, int B,
-                                               int Cin, int Cout, int HW, void* stream);
+ * gw = sum_b g[b] (x[b] * scale[b])^T (scale applied once per sample and column where the sums leave the accumulators).
+ * Partial rows of the weight gradient: Cout Cin floats each. */
+int ias_pwconv_forward(const float* x, const float* scale, const float* w, float* y, int B, int Cin, int Cout, int HW,
+                       void* stream);
+int ias_pwconv_backward_data(const float* g, const float* w, float* gx, int B, int Cin, int Cout, int HW, void* stream);
+long long ias_pwconv_weight_scratch(int B, int Cin, int Cout, int HW);
+int ias_pwconv_backward_weight(const float* g, const float* x, const float* scale, float* gw, float* scratch, int B, int Cin,
+                               int Cout, int HW, void* stream);
 
 /* The weight-gradient reductions of a whole backward pass of the trunk (torchvision mobilenet_v3_small.features, run at
  * /root/reference/audioembed.py:61; autograd of /root/reference/vicreg_audio_params.py:96-122) in ONE launch:
  * out[i] = sum_r partial[r n + i] (i < n, r < rows; fixed order) for every entry of a HOST array of `count` entries
  * holding device pointers -- the table travels in the kernel arguments (nothing is copied to the device, nothing has to
- * outlive the call; capturable).  The *_backward_weight_partials entry points leave such rows behind. */
+ * outlive the call; capturable).  The weight-gradient entries called with gw == NULL leave such rows behind. */
 typedef struct IasReduceItem {
   const float* partial;
   float* out;
@@ -711,16 +704,14 @@ int ias_conv2x2_patches_backward_nchw(const float* gp, float* gx, int B, int H, 
 /* column sums of a row-major fp32 [rows, cols] matrix in a fixed order (the bias gradient g.sum(0) of the head
  * convolutions run as GEMMs); scratch: ias_colsum_scratch_floats(rows, cols) floats */
 long long ias_colsum_scratch_floats(int rows, int cols);
-int ias_colsum(const float* a, float* out, float* scratch, int rows, int cols, void* stream);
-/* ... without its second launch: the slice sums stay in `scratch` -> their number (> 0, <= 16; `cols` floats each) for
- * ias_reduce_partials_multi (same bits as ias_colsum), or a negative IAS_ERR_*.  Reference: the bias gradient of the
+/* -> the number of slice sums left in `scratch` (> 0, <= 16; `cols` floats each), or a negative IAS_ERR_*.  out == NULL:
+ * without the second launch, the rows are for ias_reduce_partials_multi (same bits).  Reference: the bias gradient of the
  * head's nn.Conv2d(dim, dim, 2) layers, autograd of /root/reference/audioembed.py:62-68. */
-int ias_colsum_partials(const float* a, float* scratch, int rows, int cols, void* stream);
+int ias_colsum(const float* a, float* out, float* scratch, int rows, int cols, void* stream);
 int ias_stem_forward(const float* x, const float* w, float* out, int B, int H, int W, void* stream);
 long long ias_stem_weight_scratch(int B);                     /* floats */
+/* -> the number of partial rows (> 0; 432 floats each), or a negative IAS_ERR_*; gw == NULL: no reduction launch */
 int ias_stem_backward_weight(const float* x, const float* g, float* gw, float* scratch, int B, int H, int W, void* stream);
-/* ... without its reduction launch -> the number of partial rows (> 0; 432 floats each), or a negative IAS_ERR_* */
-int ias_stem_backward_weight_partials(const float* x, const float* g, float* scratch, int B, int H, int W, void* stream);
 
 /* ---- Training-mode BatchNorm2d with the following activation fused (act 0 none, 1 ReLU, 2 Hardswish): replaces the
  * nn.BatchNorm2d + activation pairs of torchvision's mobilenet_v3_small.features (audioembed.py:61) and their autograd.
@@ -728,22 +719,17 @@ int ias_stem_backward_weight_partials(const float* x, const float* g, float* scr
  * save_invstd [C]; scratch: ias_bn_scratch_doubles(B, C) doubles; sums: [C][2] floats.  Running statistics are updated
  * as torch does (momentum, unbiased variance). */
 long long ias_bn_scratch_doubles(int B, int C);
-int ias_bn_act_forward(const float* x, const float* weight, const float* bias, float* running_mean, float* running_var,
-                       float* y, float* save_mean, float* save_invstd, double* scratch, int B, int C, int HW, float eps,
-                       float momentum, int act, void* stream);
-/* the same with the block's residual connection taken in the same pass: y = act(BatchNorm_train(x)) + res (torchvision's
+/* res (or NULL): the block's residual connection taken in the same pass: y = act(BatchNorm_train(x)) + res (torchvision's
  * InvertedResidual: `result += input` behind the block's last ConvNormActivation); res [B,C,HW]; the same bits as the
- * separate addition */
-int ias_bn_act_forward_res(const float* x, const float* res, const float* weight, const float* bias, float* running_mean,
-                           float* running_var, float* y, float* save_mean, float* save_invstd, double* scratch, int B,
-                           int C, int HW, float eps, float momentum, int act, void* stream);
-/* ias_bn_act_forward that also leaves pooled[b][c] = mean over the plane of y[b][c] behind ([B,C]): the average pool of the
+ * separate addition.
+ * pooled (or NULL): also leaves pooled[b][c] = mean over the plane of y[b][c] behind ([B,C]): the average pool of the
  * squeeze-excitation block that follows a depthwise convolution's normalisation in torchvision's InvertedResidual
  * (SqueezeExcitation._scale: `self.avgpool(input)`; the trunk run at /root/reference/audioembed.py:61) -- in the
- * normalisation's own launch on maps up to 15 x 16, as ias_se_plane_reduce behind it on larger ones */
-int ias_bn_act_forward_pool(const float* x, const float* weight, const float* bias, float* running_mean, float* running_var,
-                            float* y, float* pooled, float* save_mean, float* save_invstd, double* scratch, int B, int C,
-                            int HW, float eps, float momentum, int act, void* stream);
+ * normalisation's own launch on maps up to 15 x 16, as ias_se_plane_reduce behind it on larger ones.
+ * res and pooled together: IAS_ERR_ARG (no layer of the trunk has both). */
+int ias_bn_act_forward(const float* x, const float* res, const float* weight, const float* bias, float* running_mean,
+                       float* running_var, float* y, float* pooled, float* save_mean, float* save_invstd, double* scratch,
+                       int B, int C, int HW, float eps, float momentum, int act, void* stream);
 int ias_bn_act_backward(const float* x, const float* dy, const float* weight, const float* bias, const float* save_mean,
                         const float* save_invstd, float* dx, float* gw, float* gb, double* scratch, float* sums, int B,
                         int C, int HW, int act, void* stream);

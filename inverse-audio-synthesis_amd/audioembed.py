@@ -10,8 +10,9 @@ csrc/pqmf_kernels.hip) instead of a 90 MB intermediate read + write.
 import torch
 import torch.nn as nn
 
+from . import _lib
 from .pqmf import PQMF, pqmf_analysis
-from .vision import trunk_torch
+from .vision import trunk_torch, weight_gradient
 
 
 class ChannelNormalize(nn.Module):
@@ -34,7 +35,6 @@ class _Conv2x2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, nchw=False):
-        from . import _lib
         lib = _lib.load()
         x, weight = x.contiguous(), weight.contiguous()
         _lib.require_f32(x, weight)
@@ -59,7 +59,6 @@ class _Conv2x2Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
         lib = _lib.load()
         patches, weight = ctx.saved_tensors
         B, H, W, C = ctx.shape
@@ -81,16 +80,8 @@ class _Conv2x2Fn(torch.autograd.Function):
         if ctx.has_bias and ctx.needs_input_grad[2]:
             g2c = g2.contiguous()
             gb = torch.empty(Cout, dtype=torch.float32, device=g.device)
-            scratch = torch.empty(int(lib.ias_colsum_scratch_floats(g2c.shape[0], Cout)), dtype=torch.float32, device=g.device)
-            from . import vision
-            if vision._DEFER["on"]:
-                # the second launch joins the backward pass' ONE reduction launch (vision.defer_weight_reductions)
-                srows = lib.ias_colsum_partials(_lib.ptr(g2c), _lib.ptr(scratch), g2c.shape[0], Cout, _lib.stream())
-                _lib.check(min(int(srows), 0), "ias_colsum_partials")
-                vision._defer_reduction(scratch, gb, Cout, srows)
-            else:
-                _lib.check(lib.ias_colsum(_lib.ptr(g2c), _lib.ptr(gb), _lib.ptr(scratch), g2c.shape[0], Cout, _lib.stream()),
-                           "ias_colsum")
+            # (deferring: the second launch joins the backward pass' ONE reduction launch, vision.defer_weight_reductions)
+            weight_gradient(lib.ias_colsum, lib.ias_colsum_scratch_floats(g2c.shape[0], Cout), gb, (g2c,), g2c.shape[0], Cout)
         return gx, gw, gb, None
 
 

@@ -580,32 +580,19 @@ static void bn_launch_finapply(hipStream_t stream, const float* x, const float* 
 
 // y = act(BatchNorm_train(x)); x, y [B,C,HW] fp32 contiguous; weight / bias [C] or NULL; running_mean / running_var [C]
 // or NULL (updated in place with `momentum`); save_mean / save_invstd [C] out; act 0 none, 1 ReLU, 2 Hardswish.
-static int bn_act_forward_impl(const float* x, const float* res, const float* weight, const float* bias, float* running_mean,
-                               float* running_var, float* y, float* save_mean, float* save_invstd, double* scratch, int B, int C,
-                               int HW, float eps, float momentum, int act, void* stream_, float* pooled = nullptr);
-extern "C" int ias_bn_act_forward(const float* x, const float* weight, const float* bias, float* running_mean,
-                                  float* running_var, float* y, float* save_mean, float* save_invstd, double* scratch,
-                                  int B, int C, int HW, float eps, float momentum, int act, void* stream_) {
-  return bn_act_forward_impl(x, nullptr, weight, bias, running_mean, running_var, y, save_mean, save_invstd, scratch, B, C, HW,
-                             eps, momentum, act, stream_);
-}
-// y = act(BatchNorm_train(x)) + res: the residual connection of an inverted-residual block (torchvision InvertedResidual:
-// `result += input` behind the block's last ConvNormActivation) taken in the same pass -- one elementwise launch and one
-// read + write of the map less per block; the same bits as the separate addition.  res [B,C,HW] like x, 16-byte aligned
-// where x is.
-extern "C" int ias_bn_act_forward_res(const float* x, const float* res, const float* weight, const float* bias,
-                                      float* running_mean, float* running_var, float* y, float* save_mean, float* save_invstd,
-                                      double* scratch, int B, int C, int HW, float eps, float momentum, int act, void* stream_) {
-  if (!res) return IAS_ERR_ARG;
-  return bn_act_forward_impl(x, res, weight, bias, running_mean, running_var, y, save_mean, save_invstd, scratch, B, C, HW, eps,
-                             momentum, act, stream_);
-}
+// res (or NULL): y = act(BatchNorm_train(x)) + res, the residual connection of an inverted-residual block (torchvision
+// InvertedResidual: `result += input` behind the block's last ConvNormActivation) taken in the same pass -- one elementwise
+// launch and one read + write of the map less per block; the same bits as the separate addition.  res [B,C,HW] like x,
+// 16-byte aligned where x is.
+// pooled (or NULL): also pooled[b][c] = mean_hw y[b][c] ([B,C]), the squeeze-excitation block's average pool, taken by the
+// normalisation's own launch on maps up to 15 x 16.  Not together with res (no layer of the trunk has both).
 extern "C" int ias_se_plane_reduce(const float* x, const float* m, float* out, long long planes, int HW, float scale, void* stream_);   // se_kernels.hip
-static int bn_act_forward_impl(const float* x, const float* res, const float* weight, const float* bias, float* running_mean,
-                               float* running_var, float* y, float* save_mean, float* save_invstd, double* scratch, int B, int C,
-                               int HW, float eps, float momentum, int act, void* stream_, float* pooled) {
+extern "C" int ias_bn_act_forward(const float* x, const float* res, const float* weight, const float* bias, float* running_mean,
+                                  float* running_var, float* y, float* pooled, float* save_mean, float* save_invstd,
+                                  double* scratch, int B, int C, int HW, float eps, float momentum, int act, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !y || !save_mean || !save_invstd || !scratch || B <= 0 || C <= 0 || C > 65535 || HW <= 0 || act < 0 || act > 2)
+  if (!x || !y || !save_mean || !save_invstd || !scratch || B <= 0 || C <= 0 || C > 65535 || HW <= 0 || act < 0 || act > 2 ||
+      (res && pooled))
     return IAS_ERR_ARG;
   if (const int nv = bn_fused_nv(x, y, res, B, C, HW)) {
 #define BNF_FWD(NV, POOL)                                                                                                   \
@@ -633,15 +620,6 @@ static int bn_act_forward_impl(const float* x, const float* res, const float* we
   // (maps too large for the one-workgroup-per-channel kernel: the pool as its own pass)
   if (pooled) return ias_se_plane_reduce(y, nullptr, pooled, (long long)B * C, HW, 1.0f / (float)HW, stream_);
   return IAS_OK;
-}
-// ias_bn_act_forward that also leaves pooled[b][c] = mean_hw y[b][c] behind ([B,C]): the squeeze-excitation block's average
-// pool, taken by the normalisation's own launch on maps up to 15 x 16
-extern "C" int ias_bn_act_forward_pool(const float* x, const float* weight, const float* bias, float* running_mean,
-                                       float* running_var, float* y, float* pooled, float* save_mean, float* save_invstd,
-                                       double* scratch, int B, int C, int HW, float eps, float momentum, int act, void* stream_) {
-  if (!pooled) return IAS_ERR_ARG;
-  return bn_act_forward_impl(x, nullptr, weight, bias, running_mean, running_var, y, save_mean, save_invstd, scratch, B, C, HW,
-                             eps, momentum, act, stream_, pooled);
 }
 
 // Backward of ias_bn_act_forward: dy [B,C,HW] -> dx [B,C,HW], gw / gb [C] (either may be NULL); sums [C][2] floats scratch.

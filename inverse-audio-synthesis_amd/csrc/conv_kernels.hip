@@ -606,7 +606,7 @@ __global__ __launch_bounds__(CV_THREADS) void stem_fwd_kernel(const float* __res
 }
 
 // The VALU / LDS form of the stem weight gradient: superseded by stem_bwd_weight_mfma_kernel, instantiated by the diagnostic
-// library only (stem_backward_weight: IAS_STEM_GW_LDS).
+// library only (ias_stem_backward_weight: IAS_STEM_GW_LDS).
 // partial[chunk][co][ci*9+kh*3+kw]: a workgroup stages 256 positions (27 inputs + COUT cotangents each) in LDS, then
 // thread t < COUT*27 sums its weight element over them; grid (position chunks, B).
 template <int CIN, int COUT>
@@ -1110,9 +1110,10 @@ extern "C" long long ias_dwconv_weight_scratch_hw(int B, int C, int H, int W, in
 }
 
 // its gradient w.r.t. the weights: x [B,C,H,W], g [B,C,Ho,Wo] -> gw [C,1,K,K]; scratch: ias_dwconv_weight_scratch_hw floats
-// gw == nullptr: the partial sums only -> *nrows rows of C K K floats in `scratch` (ias_dwconv_backward_weight_partials)
-static int dw_backward_weight(const float* x, const float* g, float* gw, float* scratch, int B, int C, int H, int W, int K,
-                              int S, int* nrows, void* stream_) {
+// -> the number of partial rows left in `scratch` (> 0; C K K floats each), or a negative status.  gw == NULL: without the
+// reduction launch, the rows are for ias_reduce_partials_multi
+extern "C" int ias_dwconv_backward_weight(const float* x, const float* g, float* gw, float* scratch, int B, int C, int H,
+                                          int W, int K, int S, void* stream_) {
   int rc = cv_check(x, g, scratch, B, C, H, W, K, S);
   if (rc) return rc;
   const int Ho = ias_conv_out_size(H, K, S), Wo = ias_conv_out_size(W, K, S);
@@ -1129,34 +1130,19 @@ static int dw_backward_weight(const float* x, const float* g, float* gw, float* 
     DW_WAVE_DISPATCH(1, wg, dim3(dw_wave_grid(wg, nwork)), dim3(64), wg.lds, (hipStream_t)stream_, x, (const float*)nullptr, g, scratch, B,
                      C, H, W, Ho, Wo, 0, wg, nwork);
     const int n = C * K * K;
-    if (nrows) *nrows = nchunk;
     if (gw)
       hipLaunchKernelGGL(conv_reduce_partials_kernel, dim3((n + 3) / 4), dim3(CV_THREADS), 0, (hipStream_t)stream_, scratch, gw, n,
                          nchunk);
-    return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
+    return hipGetLastError() == hipSuccess ? nchunk : IAS_ERR_LAUNCH;
   }
   const DwTile t = dw_tile_geometry(H, W, Ho, Wo, K, S, 1);
   DW_TILE_DISPATCH(1, dim3((planes + t.pp - 1) / t.pp, t.ntiles), dim3(CV_THREADS), t.lds, (hipStream_t)stream_, x,
                    (const float*)nullptr, g, scratch, C, H, W, Ho, Wo, planes, t.pp, t.rows_out, t.Wp, 0, t.mWp, t.mRows);
   const int n = C * K * K;   // scratch is [tile][b][c][K K]: the partials of a channel are n floats apart
-  if (nrows) *nrows = B * t.ntiles;
   if (gw)
     hipLaunchKernelGGL(conv_reduce_partials_kernel, dim3((n + 3) / 4), dim3(CV_THREADS), 0, (hipStream_t)stream_, scratch, gw,
                        n, B * t.ntiles);
-  return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
-}
-extern "C" int ias_dwconv_backward_weight(const float* x, const float* g, float* gw, float* scratch, int B, int C, int H,
-                                          int W, int K, int S, void* stream_) {
-  if (!gw) return IAS_ERR_ARG;
-  return dw_backward_weight(x, g, gw, scratch, B, C, H, W, K, S, nullptr, stream_);
-}
-// The same without the reduction launch: -> the number of partial rows (> 0; C K K floats each) for
-// ias_reduce_partials_multi, or a negative status
-extern "C" int ias_dwconv_backward_weight_partials(const float* x, const float* g, float* scratch, int B, int C, int H, int W,
-                                                   int K, int S, void* stream_) {
-  int nrows = 0;
-  const int rc = dw_backward_weight(x, g, nullptr, scratch, B, C, H, W, K, S, &nrows, stream_);
-  return rc != IAS_OK ? rc : nrows;
+  return hipGetLastError() == hipSuccess ? B * t.ntiles : IAS_ERR_LAUNCH;
 }
 
 // Stem Conv2d(3, 16, 3, stride 2, padding 1, bias=False): x [B,3,H,W], w [16,3,3,3] -> out [B,16,Ho,Wo]
@@ -1191,18 +1177,18 @@ extern "C" int ias_stem_forward(const float* x, const float* w, float* out, int 
 extern "C" long long ias_stem_weight_scratch(int B) { return B <= 0 ? IAS_ERR_ARG : (long long)B * STEM_CHUNKS_X * 432; }
 
 // its weight gradient: x [B,3,H,W], g [B,16,Ho,Wo] -> gw [16,3,3,3]; scratch: ias_stem_weight_scratch(B) floats
-// gw == nullptr: the partial sums only -> *nrows rows of 432 floats in `scratch` (ias_stem_backward_weight_partials)
-static int stem_backward_weight(const float* x, const float* g, float* gw, float* scratch, int B, int H, int W, int* nrows,
-                                void* stream_) {
+// -> the number of partial rows left in `scratch` (> 0; 432 floats each), or a negative status.  gw == NULL: without the
+// reduction launch, the rows are for ias_reduce_partials_multi
+extern "C" int ias_stem_backward_weight(const float* x, const float* g, float* gw, float* scratch, int B, int H, int W,
+                                        void* stream_) {
   if (!x || !g || !scratch || B <= 0 || B > 65535 || H <= 0 || W <= 0) return IAS_ERR_ARG;
   const int Ho = ias_conv_out_size(H, 3, 2), Wo = ias_conv_out_size(W, 3, 2);
   // the partial rows are in `scratch`: report them, reduce them where the caller wants the gradient itself
   auto finish = [&](int rows) {
-    if (nrows) *nrows = rows;
     if (gw)
       hipLaunchKernelGGL(conv_reduce_partials_kernel, dim3((432 + 3) / 4), dim3(CV_THREADS), 0, (hipStream_t)stream_, scratch, gw,
                          432, rows);
-    return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
+    return hipGetLastError() == hipSuccess ? rows : IAS_ERR_LAUNCH;
   };
   if constexpr (kIasDiag) {   // IAS_STEM_GW_LDS: the VALU / LDS form
     if (ias_diag_env("IAS_STEM_GW_LDS")) {
@@ -1231,18 +1217,6 @@ static int stem_backward_weight(const float* x, const float* g, float* gw, float
                      dim3(CV_THREADS), 0, (hipStream_t)stream_, x, g, scratch, B, H, W, Ho, Wo, STEM_CHUNKS_X,
                      rows_per_chunk);
   return finish(B * STEM_CHUNKS_X);
-}
-extern "C" int ias_stem_backward_weight(const float* x, const float* g, float* gw, float* scratch, int B, int H, int W,
-                                        void* stream_) {
-  if (!gw) return IAS_ERR_ARG;
-  return stem_backward_weight(x, g, gw, scratch, B, H, W, nullptr, stream_);
-}
-// The same without the reduction launch: -> the number of partial rows (> 0; 432 floats each), or a negative status
-extern "C" int ias_stem_backward_weight_partials(const float* x, const float* g, float* scratch, int B, int H, int W,
-                                                 void* stream_) {
-  int nrows = 0;
-  const int rc = stem_backward_weight(x, g, nullptr, scratch, B, H, W, &nrows, stream_);
-  return rc != IAS_OK ? rc : nrows;
 }
 
 // ---- head: Conv2d(C, Cout, kernel 2) on channels-last maps as one GEMM (audioembed.py: conv7 .. conv1) -------------
@@ -1429,26 +1403,15 @@ extern "C" long long ias_colsum_scratch_floats(int rows, int cols) {
   if (rows <= 0 || cols <= 0) return IAS_ERR_ARG;
   return (long long)colsum_slices(rows) * cols;
 }
-// out == nullptr: the slice sums only (S rows of `cols` floats in scratch)
-static int colsum_launch(const float* a, float* out, float* scratch, int rows, int cols, int* nrows, void* stream_) {
+// -> the number of slice rows left in `scratch` (> 0, <= 16; `cols` floats each, in slice order), or a negative IAS_ERR_*.
+// out == NULL: without the second launch, the rows are for ias_reduce_partials_multi (which adds <= 16 rows in row order,
+// as the second launch does: the same bits)
+extern "C" int ias_colsum(const float* a, float* out, float* scratch, int rows, int cols, void* stream_) {
   if (!a || !scratch || rows <= 0 || cols <= 0) return IAS_ERR_ARG;
   const int S = colsum_slices(rows);
   const int rps = (rows + S - 1) / S;
   hipLaunchKernelGGL(colsum_partial_kernel, dim3((cols + CS_CT - 1) / CS_CT, S), dim3(CS_CT * CS_RG), 0, (hipStream_t)stream_, a,
                      scratch, rows, cols, rps);
   if (out) hipLaunchKernelGGL(colsum_finish_kernel, dim3((cols + 255) / 256), dim3(256), 0, (hipStream_t)stream_, scratch, out, S, cols);
-  if (nrows) *nrows = S;
-  return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
-}
-extern "C" int ias_colsum(const float* a, float* out, float* scratch, int rows, int cols, void* stream_) {
-  if (!out) return IAS_ERR_ARG;
-  return colsum_launch(a, out, scratch, rows, cols, nullptr, stream_);
-}
-// The same without its second launch -> the number of slice rows (> 0; `cols` floats each, in slice order) left in
-// `scratch` for ias_reduce_partials_multi (which adds <= 16 rows in row order, as the second launch does: the same bits),
-// or a negative IAS_ERR_*
-extern "C" int ias_colsum_partials(const float* a, float* scratch, int rows, int cols, void* stream_) {
-  int S = 0;
-  const int rc = colsum_launch(a, nullptr, scratch, rows, cols, &S, stream_);
-  return rc != IAS_OK ? rc : S;
+  return hipGetLastError() == hipSuccess ? S : IAS_ERR_LAUNCH;
 }

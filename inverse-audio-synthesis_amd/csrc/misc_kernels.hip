@@ -2,7 +2,7 @@
 // achievable HBM rate on the box it runs on (MI355X_MICROARCH: 6.29 TB/s float4 copy).
 #include "ias_common.h"
 
-#define IAS_VERSION 101
+#define IAS_VERSION 102
 
 extern "C" int ias_version(void) { return IAS_VERSION; }
 

@@ -397,17 +397,12 @@ static int pw_apply(const float* x, const float* xs, const float* w, float* y, i
 }
 
 // Conv2d(Cin, Cout, 1, bias=False) forward: x [B,Cin,HW], w [Cout,Cin] -> y [B,Cout,HW]
-extern "C" int ias_pwconv_forward(const float* x, const float* w, float* y, int B, int Cin, int Cout, int HW, void* stream_) {
-  if (!x || !w || !y || B <= 0 || HW <= 0) return IAS_ERR_ARG;
-  if (!ias_pwconv_supported(Cin, Cout)) return IAS_ERR_UNSUPPORTED;
-  return pw_apply(x, nullptr, w, y, B, Cout, Cin, HW, 0, (hipStream_t)stream_);
-}
-// The same on a gated input: y[b] = W (x[b] * scale[b]), scale [B,Cin] -- the projection behind a squeeze-excitation block
-// (torchvision InvertedResidual: SqueezeExcitation -> Conv2dNormActivation(cexp, cout, 1); reference: the trunk of
+// scale (or NULL): on a gated input, y[b] = W (x[b] * scale[b]), scale [B,Cin] -- the projection behind a squeeze-excitation
+// block (torchvision InvertedResidual: SqueezeExcitation -> Conv2dNormActivation(cexp, cout, 1); reference: the trunk of
 // /root/reference/audioembed.py:61) without the gate's own pass over the expanded map.
-extern "C" int ias_pwconv_forward_scaled(const float* x, const float* scale, const float* w, float* y, int B, int Cin, int Cout,
-                                         int HW, void* stream_) {
-  if (!x || !scale || !w || !y || B <= 0 || HW <= 0) return IAS_ERR_ARG;
+extern "C" int ias_pwconv_forward(const float* x, const float* scale, const float* w, float* y, int B, int Cin, int Cout, int HW,
+                                  void* stream_) {
+  if (!x || !w || !y || B <= 0 || HW <= 0) return IAS_ERR_ARG;
   if (!ias_pwconv_supported(Cin, Cout)) return IAS_ERR_UNSUPPORTED;
   return pw_apply(x, scale, w, y, B, Cout, Cin, HW, 0, (hipStream_t)stream_);
 }
@@ -434,8 +429,6 @@ extern "C" long long ias_pwconv_weight_scratch(int B, int Cin, int Cout, int HW)
   return (long long)B * pw_wgrad_splits(B, Cout, HW) * Cin * Cout;
 }
 
-// its weight gradient: g [B,Cout,HW], x [B,Cin,HW] -> gw [Cout,Cin]; scratch: ias_pwconv_weight_scratch floats.
-// gw == nullptr: the partial sums only -> *nchunk rows of Cout Cin floats in `scratch` (ias_pwconv_backward_weight_partials)
 template <bool SCALED>
 static void pw_wgrad_launch(int vec, long long grid, size_t lds, hipStream_t st, const float* g, const float* x, const float* xs,
                             float* scratch, int B, int Cout, int Cin, int HW, int splits, int cps) {
@@ -445,9 +438,12 @@ static void pw_wgrad_launch(int vec, long long grid, size_t lds, hipStream_t st,
     default: hipLaunchKernelGGL((pw_wgrad_kernel<1, SCALED>), dim3((unsigned)grid), dim3(PW_THREADS), lds, st, g, x, xs, scratch, B, Cout, Cin, HW, splits, cps); break;
   }
 }
-// xs: NULL, or the [B][Cin] scale of the forward's gated input (ias_pwconv_forward_scaled)
-static int pw_backward_weight(const float* g, const float* x, const float* xs, float* gw, float* scratch, int B, int Cin, int Cout, int HW,
-                              int* nchunk, void* stream_) {
+// its weight gradient: g [B,Cout,HW], x [B,Cin,HW] -> gw [Cout,Cin]; scratch: ias_pwconv_weight_scratch floats.
+// scale: NULL, or the [B][Cin] scale of the forward's gated input: gw = sum_b g[b] (x[b] * scale[b])^T
+// -> the number of partial rows left in `scratch` (> 0; row r is scratch[r Cout Cin ...]), or a negative status.  gw == NULL:
+// without the reduction launch, the rows are for ias_reduce_partials_multi
+extern "C" int ias_pwconv_backward_weight(const float* g, const float* x, const float* scale, float* gw, float* scratch, int B,
+                                          int Cin, int Cout, int HW, void* stream_) {
   if (!g || !x || !scratch || B <= 0 || HW <= 0) return IAS_ERR_ARG;
   if (!ias_pwconv_supported(Cin, Cout)) return IAS_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream_;
@@ -456,48 +452,21 @@ static int pw_backward_weight(const float* g, const float* x, const float* xs, f
   const long long units = (long long)B * splits, ugroups = (units + PW_THREADS / 64 - 1) / (PW_THREADS / 64);
   const long long grid = ugroups * T;
   if (grid > 0x7fffffffLL) return IAS_ERR_ARG;
-  const size_t lds = sizeof(float) * (size_t)(PW_THREADS / 64) * (NTI * 256 + (xs ? 256 : 0));   // (+ the waves' scale rows)
-  if (xs) pw_wgrad_launch<true>(pw_vec(g, x, HW), grid, lds, st, g, x, xs, scratch, B, Cout, Cin, HW, splits, cps);
-  else pw_wgrad_launch<false>(pw_vec(g, x, HW), grid, lds, st, g, x, xs, scratch, B, Cout, Cin, HW, splits, cps);
-  if (nchunk) *nchunk = (int)ugroups;
+  const size_t lds = sizeof(float) * (size_t)(PW_THREADS / 64) * (NTI * 256 + (scale ? 256 : 0));   // (+ the waves' scale rows)
+  if (scale) pw_wgrad_launch<true>(pw_vec(g, x, HW), grid, lds, st, g, x, scale, scratch, B, Cout, Cin, HW, splits, cps);
+  else pw_wgrad_launch<false>(pw_vec(g, x, HW), grid, lds, st, g, x, scale, scratch, B, Cout, Cin, HW, splits, cps);
   if (gw) {
     const int n = Cout * Cin;
     hipLaunchKernelGGL(pw_reduce_partials_kernel, dim3((n + 15) / 16), dim3(PW_THREADS), 0, st, scratch, gw, n, (int)ugroups);
   }
-  return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
-}
-extern "C" int ias_pwconv_backward_weight(const float* g, const float* x, float* gw, float* scratch, int B, int Cin, int Cout,
-                                          int HW, void* stream_) {
-  if (!gw) return IAS_ERR_ARG;
-  return pw_backward_weight(g, x, nullptr, gw, scratch, B, Cin, Cout, HW, nullptr, stream_);
-}
-// the weight gradient of ias_pwconv_forward_scaled: gw = sum_b g[b] (x[b] * scale[b])^T
-extern "C" int ias_pwconv_backward_weight_scaled(const float* g, const float* x, const float* scale, float* gw, float* scratch,
-                                                 int B, int Cin, int Cout, int HW, void* stream_) {
-  if (!gw || !scale) return IAS_ERR_ARG;
-  return pw_backward_weight(g, x, scale, gw, scratch, B, Cin, Cout, HW, nullptr, stream_);
-}
-// The same without the reduction launch: -> the number of partial rows (> 0; row r is scratch[r Cout Cin ...]) for
-// ias_reduce_partials_multi, or a negative status
-extern "C" int ias_pwconv_backward_weight_partials(const float* g, const float* x, float* scratch, int B, int Cin, int Cout,
-                                                   int HW, void* stream_) {
-  int nchunk = 0;
-  const int rc = pw_backward_weight(g, x, nullptr, nullptr, scratch, B, Cin, Cout, HW, &nchunk, stream_);
-  return rc != IAS_OK ? rc : nchunk;
-}
-extern "C" int ias_pwconv_backward_weight_partials_scaled(const float* g, const float* x, const float* scale, float* scratch,
-                                                          int B, int Cin, int Cout, int HW, void* stream_) {
-  if (!scale) return IAS_ERR_ARG;
-  int nchunk = 0;
-  const int rc = pw_backward_weight(g, x, scale, nullptr, scratch, B, Cin, Cout, HW, &nchunk, stream_);
-  return rc != IAS_OK ? rc : nchunk;
+  return hipGetLastError() == hipSuccess ? (int)ugroups : IAS_ERR_LAUNCH;
 }
 
 // ---- the weight-gradient reductions of a whole backward pass in ONE launch ------------------------------------------
 // Every weight gradient of the trunk (thin 1x1, depthwise, stem) ends in out[i] = sum_r partial[r n + i], a launch of
-// 5-6 us that is all latency, 27 of them on the backward's dependency chain per pretraining step.  The *_partials entry
-// points leave the partial rows behind; this kernel folds all of them: a workgroup per 16 outputs of one item, the
-// arithmetic of pw_reduce_partials_kernel (fixed order: deterministic).  The table travels BY VALUE in the kernel
+// 5-6 us that is all latency, 27 of them on the backward's dependency chain per pretraining step.  The weight-gradient
+// entry points called with gw == NULL leave the partial rows behind; this kernel folds all of them: a workgroup per 16
+// outputs of one item, the arithmetic of pw_reduce_partials_kernel (fixed order: deterministic).  The table travels BY VALUE in the kernel
 // arguments (2.7 KB of the 4 KB a launch may carry): no device table, no staging copy, nothing to keep alive for a
 // captured graph, and nothing allocated while a capture is open.
 #define IAS_REDUCE_MAX_ITEMS 96

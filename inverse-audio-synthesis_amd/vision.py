@@ -18,6 +18,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib
+
 # Diagnostics only (scripts/diag set these attributes; nothing in the package or the environment does): every layer of the
 # trunk AND the conv head of audioembed.py on their torch.nn parents (MIOpen / rocBLAS) / the thin 1x1 convolutions as
 # batched GEMMs -- for A/B timing against the HIP kernels.
@@ -33,7 +35,7 @@ def trunk_torch():
 # Every weight gradient of the trunk (thin 1x1, depthwise, stem) ends in a reduction of per-workgroup partial rows: a launch
 # of 5-6 us, all latency, 27 of them on the dependency chain of a pretraining step's backward.  With
 # ``defer_weight_reductions(True)`` the backward functions below leave their partial rows behind
-# (``ias_*_backward_weight_partials``), hand autograd the still unwritten gradient tensor, and ONE
+# (``ias_*_backward_weight`` without a gradient pointer), hand autograd the still unwritten gradient tensor, and ONE
 # ``ias_reduce_partials_multi`` launch fills all of them from a callback the autograd engine runs when the backward pass is
 # over (``queue_callback``: before ``backward()`` / ``autograd.grad()`` returns, also inside a hipGraph capture).  Nothing
 # may READ a weight gradient during the backward pass, then: a post-accumulate-grad hook would (dist.GradBucketer on
@@ -65,7 +67,6 @@ def _flush_reductions():
     items, _DEFER["items"] = _DEFER["items"], []
     if not items:
         return
-    from . import _lib
     lib = _lib.load()
     # a HOST table: the library passes it to the kernel by value (no device table, no staging copy: nothing is allocated
     # here, which matters inside a hipGraph capture -- pinned memory must not be allocated while one is open)
@@ -74,6 +75,17 @@ def _flush_reductions():
         t.partial, t.out, t.n, t.rows = s.data_ptr(), gp, n, r
     _lib.check(lib.ias_reduce_partials_multi(ctypes.cast(table, ctypes.c_void_p), len(items), _lib.stream()),
                "ias_reduce_partials_multi")
+
+
+def weight_gradient(entry, scratch_floats, gw, inputs, *dims):
+    """Fill the still unwritten ``gw`` through one of the library's weight-gradient entries,
+    ``entry(*inputs, gw, scratch, *dims, stream)`` -> partial rows: the entry reduces its rows itself, or -- under
+    ``defer_weight_reductions(True)`` -- gets no gradient pointer and its rows join the pass' one reduction launch."""
+    scratch = torch.empty(int(scratch_floats), dtype=torch.float32, device=gw.device)
+    rows = int(entry(*map(_lib.ptr, inputs), None if _DEFER["on"] else _lib.ptr(gw), _lib.ptr(scratch), *dims, _lib.stream()))
+    _lib.check(min(rows, 0), entry.__name__)
+    if _DEFER["on"]:
+        _defer_reduction(scratch, gw, gw.numel(), rows)
 
 
 _PW_SUPPORTED = {}
@@ -85,7 +97,6 @@ def _pw_mfma(cin, cout):
         return False
     key = (cin, cout)
     if key not in _PW_SUPPORTED:
-        from . import _lib
         _PW_SUPPORTED[key] = bool(_lib.load().ias_pwconv_supported(cin, cout))
     return _PW_SUPPORTED[key]
 
@@ -96,21 +107,19 @@ class _PointwiseFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w):
-        from . import _lib
         lib = _lib.load()
         x, w = x.contiguous(), w.contiguous()
         _lib.require_f32(x, w)
         B, C, H, W = x.shape
         Cout = w.shape[0]
         y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-        _lib.check(lib.ias_pwconv_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(y), B, C, Cout, H * W, _lib.stream()),
+        _lib.check(lib.ias_pwconv_forward(_lib.ptr(x), None, _lib.ptr(w), _lib.ptr(y), B, C, Cout, H * W, _lib.stream()),
                    "ias_pwconv_forward")
         ctx.save_for_backward(x, w)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
         lib = _lib.load()
         x, w = ctx.saved_tensors
         g = g.contiguous()
@@ -123,15 +132,8 @@ class _PointwiseFn(torch.autograd.Function):
                        "ias_pwconv_backward_data")
         if ctx.needs_input_grad[1]:
             gw = torch.empty_like(w)
-            scratch = torch.empty(int(lib.ias_pwconv_weight_scratch(B, C, Cout, H * W)), dtype=torch.float32, device=x.device)
-            if _DEFER["on"]:
-                rows = lib.ias_pwconv_backward_weight_partials(_lib.ptr(g), _lib.ptr(x), _lib.ptr(scratch), B, C, Cout, H * W,
-                                                               _lib.stream())
-                _lib.check(min(int(rows), 0), "ias_pwconv_backward_weight_partials")
-                _defer_reduction(scratch, gw, gw.numel(), rows)
-            else:
-                _lib.check(lib.ias_pwconv_backward_weight(_lib.ptr(g), _lib.ptr(x), _lib.ptr(gw), _lib.ptr(scratch), B, C, Cout,
-                                                          H * W, _lib.stream()), "ias_pwconv_backward_weight")
+            weight_gradient(lib.ias_pwconv_backward_weight, lib.ias_pwconv_weight_scratch(B, C, Cout, H * W), gw, (g, x, None),
+                            B, C, Cout, H * W)
         return gx, gw
 
 
@@ -163,7 +165,6 @@ class _DepthwiseFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, K, S):
-        from . import _lib
         lib = _lib.load()
         x, w = x.contiguous(), w.contiguous()
         _lib.require_f32(x, w)
@@ -178,7 +179,6 @@ class _DepthwiseFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
         lib = _lib.load()
         x, w = ctx.saved_tensors
         K, S = ctx.ks
@@ -191,15 +191,8 @@ class _DepthwiseFn(torch.autograd.Function):
                        "ias_dwconv_backward_data")
         if ctx.needs_input_grad[1]:
             gw = torch.empty_like(w)
-            scratch = torch.empty(int(lib.ias_dwconv_weight_scratch_hw(B, C, H, W, K, S)), dtype=torch.float32, device=x.device)
-            if _DEFER["on"]:
-                rows = lib.ias_dwconv_backward_weight_partials(_lib.ptr(x), _lib.ptr(g), _lib.ptr(scratch), B, C, H, W, K, S,
-                                                               _lib.stream())
-                _lib.check(min(int(rows), 0), "ias_dwconv_backward_weight_partials")
-                _defer_reduction(scratch, gw, gw.numel(), rows)
-            else:
-                _lib.check(lib.ias_dwconv_backward_weight(_lib.ptr(x), _lib.ptr(g), _lib.ptr(gw), _lib.ptr(scratch), B, C, H, W,
-                                                          K, S, _lib.stream()), "ias_dwconv_backward_weight")
+            weight_gradient(lib.ias_dwconv_backward_weight, lib.ias_dwconv_weight_scratch_hw(B, C, H, W, K, S), gw, (x, g),
+                            B, C, H, W, K, S)
         return gx, gw, None, None
 
 
@@ -221,7 +214,6 @@ class DepthwiseConv2d(nn.Conv2d):
 class _StemFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w):
-        from . import _lib
         lib = _lib.load()
         x, w = x.contiguous(), w.contiguous()
         _lib.require_f32(x, w)
@@ -234,7 +226,6 @@ class _StemFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
         lib = _lib.load()
         x, w = ctx.saved_tensors
         B, _c, H, W = x.shape
@@ -244,14 +235,7 @@ class _StemFn(torch.autograd.Function):
             gx = torch.nn.grad.conv2d_input(x.shape, w, g, stride=2, padding=1)
         if ctx.needs_input_grad[1]:
             gw = torch.empty_like(w)
-            scratch = torch.empty(int(lib.ias_stem_weight_scratch(B)), dtype=torch.float32, device=x.device)
-            if _DEFER["on"]:
-                rows = lib.ias_stem_backward_weight_partials(_lib.ptr(x), _lib.ptr(g), _lib.ptr(scratch), B, H, W, _lib.stream())
-                _lib.check(min(int(rows), 0), "ias_stem_backward_weight_partials")
-                _defer_reduction(scratch, gw, gw.numel(), rows)
-            else:
-                _lib.check(lib.ias_stem_backward_weight(_lib.ptr(x), _lib.ptr(g), _lib.ptr(gw), _lib.ptr(scratch), B, H, W,
-                                                        _lib.stream()), "ias_stem_backward_weight")
+            weight_gradient(lib.ias_stem_backward_weight, lib.ias_stem_weight_scratch(B), gw, (x, g), B, H, W)
         return gx, gw
 
 
@@ -272,7 +256,6 @@ class _BNActFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, act, res=None, pool=False):
-        from . import _lib
         lib = _lib.load()
         x = x.contiguous()
         B, C = x.shape[0], x.shape[1]
@@ -287,23 +270,14 @@ class _BNActFn(torch.autograd.Function):
             # differentiable output: the block's backward (_SEFn / _SEProjFn) carries the pool's gradient itself
             assert res is None
             pooled = torch.empty((B, C), dtype=torch.float32, device=x.device)
-            _lib.check(lib.ias_bn_act_forward_pool(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(running_mean),
-                                                   _lib.ptr(running_var), _lib.ptr(y), _lib.ptr(pooled), _lib.ptr(mean),
-                                                   _lib.ptr(invstd), _lib.ptr(scratch), B, C, HW, float(eps), float(momentum),
-                                                   int(act), _lib.stream()), "ias_bn_act_forward_pool")
         elif res is not None:
             # the block's residual connection in the same pass: y = act(bn(x)) + res
             res = res.contiguous()
             assert res.shape == x.shape
-            _lib.check(lib.ias_bn_act_forward_res(_lib.ptr(x), _lib.ptr(res), _lib.ptr(weight), _lib.ptr(bias),
-                                                  _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(y), _lib.ptr(mean),
-                                                  _lib.ptr(invstd), _lib.ptr(scratch), B, C, HW, float(eps), float(momentum),
-                                                  int(act), _lib.stream()), "ias_bn_act_forward_res")
-        else:
-            _lib.check(lib.ias_bn_act_forward(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(running_mean),
-                                              _lib.ptr(running_var), _lib.ptr(y), _lib.ptr(mean), _lib.ptr(invstd),
-                                              _lib.ptr(scratch), B, C, HW, float(eps), float(momentum), int(act),
-                                              _lib.stream()), "ias_bn_act_forward")
+        _lib.check(lib.ias_bn_act_forward(_lib.ptr(x), _lib.ptr(res), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(running_mean),
+                                          _lib.ptr(running_var), _lib.ptr(y), _lib.ptr(pooled), _lib.ptr(mean), _lib.ptr(invstd),
+                                          _lib.ptr(scratch), B, C, HW, float(eps), float(momentum), int(act), _lib.stream()),
+                   "ias_bn_act_forward")
         ctx.save_for_backward(x, weight, bias, mean, invstd)
         ctx.act = int(act)
         ctx.has_res = res is not None
@@ -318,7 +292,6 @@ class _BNActFn(torch.autograd.Function):
     def backward(ctx, g, _g_pooled=None):
         if g is None:
             return (None,) * 10
-        from . import _lib
         lib = _lib.load()
         x, weight, bias, mean, invstd = ctx.saved_tensors
         g = g.contiguous()
@@ -414,6 +387,49 @@ class ConvBNAct(nn.Sequential):
         super().__init__(*layers)
 
 
+def _gate_forward(x, w1, b1, w2, b2, pooled):
+    """The squeeze-excitation gate s = hardsigmoid(fc2(relu(fc1(mean_hw x)))) of x [B,C,H,W] -> pooled, h, z, s (what its
+    backward needs).  ``pooled``: x.mean((2, 3)) as the layer in front left it behind (BatchNormAct2d.forward(pool=True)),
+    or None: taken here."""
+    lib = _lib.load()
+    B, C, H, W = x.shape
+    hw = H * W
+    Cs = w1.shape[0]
+    if pooled is None:
+        pooled = torch.empty((B, C), dtype=torch.float32, device=x.device)
+        _lib.check(lib.ias_se_plane_reduce(_lib.ptr(x), None, _lib.ptr(pooled), B * C, hw, 1.0 / hw, _lib.stream()),
+                   "ias_se_plane_reduce")
+    h = torch.empty((B, Cs), dtype=torch.float32, device=x.device)
+    z, s = torch.empty_like(pooled), torch.empty_like(pooled)
+    _lib.check(lib.ias_se_mlp_forward(_lib.ptr(pooled), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(h),
+                                      _lib.ptr(z), _lib.ptr(s), B, C, Cs, _lib.stream()), "ias_se_mlp_forward")
+    return pooled, h, z, s
+
+
+def _gate_backward(gy, x, pooled, h, z, s, w1, w2):
+    """From the cotangent gy of the gated map x * s -> gx, gw1, gb1, gw2, gb2: the per-plane <gy, x>, the gate's two 1x1
+    convolutions backward, and gx = gy s + gpool / HW."""
+    lib = _lib.load()
+    B, C, H, W = x.shape
+    hw = H * W
+    Cs = w1.shape[0]
+    gs = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    _lib.check(lib.ias_se_plane_reduce(_lib.ptr(gy), _lib.ptr(x), _lib.ptr(gs), B * C, hw, 1.0, _lib.stream()),
+               "ias_se_plane_reduce")
+    gz, gp = torch.empty_like(gs), torch.empty_like(gs)
+    gh = torch.empty((B, Cs), dtype=torch.float32, device=x.device)
+    gw1, gw2 = torch.empty_like(w1), torch.empty_like(w2)
+    gb1 = torch.empty(Cs, dtype=torch.float32, device=x.device)
+    gb2 = torch.empty(C, dtype=torch.float32, device=x.device)
+    _lib.check(lib.ias_se_mlp_backward(_lib.ptr(gs), _lib.ptr(z), _lib.ptr(h), _lib.ptr(pooled), _lib.ptr(w1), _lib.ptr(w2),
+                                       _lib.ptr(gz), _lib.ptr(gh), _lib.ptr(gp), _lib.ptr(gw1), _lib.ptr(gb1), _lib.ptr(gw2),
+                                       _lib.ptr(gb2), B, C, Cs, _lib.stream()), "ias_se_mlp_backward")
+    gx = torch.empty_like(x)
+    _lib.check(lib.ias_se_scale(_lib.ptr(gy), _lib.ptr(s), _lib.ptr(gp), _lib.ptr(gx), B * C, hw, 1.0 / hw, _lib.stream()),
+               "ias_se_scale")
+    return gx, gw1, gb1, gw2, gb2
+
+
 class _SEFn(torch.autograd.Function):
     """y = x * hardsigmoid(fc2(relu(fc1(mean_hw x)))), all of it in csrc/se_kernels.hip: the passes over x (pool, scale,
     and in backward the per-plane <gy, x> and gx = gy s + gpool / HW, one pass each) and the two 1x1 convolutions on
@@ -421,94 +437,51 @@ class _SEFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, pooled=None):
-        from . import _lib
         lib = _lib.load()
-        x = x.contiguous()
+        x, w1, w2 = x.contiguous(), w1.contiguous(), w2.contiguous()
         _lib.require_f32(x, w1, b1, w2, b2)
         B, C, H, W = x.shape
-        hw = H * W
-        Cs = w1.shape[0]
-        w1, w2 = w1.contiguous(), w2.contiguous()
-        if pooled is None:          # (else: x.mean((2, 3)) as the layer in front left it behind, BatchNormAct2d.forward(pool=True))
-            pooled = torch.empty((B, C), dtype=torch.float32, device=x.device)
-            _lib.check(lib.ias_se_plane_reduce(_lib.ptr(x), None, _lib.ptr(pooled), B * C, hw, 1.0 / hw, _lib.stream()),
-                       "ias_se_plane_reduce")
-        h = torch.empty((B, Cs), dtype=torch.float32, device=x.device)
-        z, s = torch.empty_like(pooled), torch.empty_like(pooled)
-        _lib.check(lib.ias_se_mlp_forward(_lib.ptr(pooled), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(h),
-                                          _lib.ptr(z), _lib.ptr(s), B, C, Cs, _lib.stream()), "ias_se_mlp_forward")
+        pooled, h, z, s = _gate_forward(x, w1, b1, w2, b2, pooled)
         y = torch.empty_like(x)
-        _lib.check(lib.ias_se_scale(_lib.ptr(x), _lib.ptr(s), None, _lib.ptr(y), B * C, hw, 0.0, _lib.stream()), "ias_se_scale")
+        _lib.check(lib.ias_se_scale(_lib.ptr(x), _lib.ptr(s), None, _lib.ptr(y), B * C, H * W, 0.0, _lib.stream()), "ias_se_scale")
         ctx.save_for_backward(x, pooled, h, z, s, w1, w2)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        from . import _lib
-        lib = _lib.load()
-        x, pooled, h, z, s, w1, w2 = ctx.saved_tensors
-        gy = gy.contiguous()
-        B, C, H, W = x.shape
-        hw = H * W
-        Cs = w1.shape[0]
-        gs = torch.empty((B, C), dtype=torch.float32, device=x.device)
-        _lib.check(lib.ias_se_plane_reduce(_lib.ptr(gy), _lib.ptr(x), _lib.ptr(gs), B * C, hw, 1.0, _lib.stream()),
-                   "ias_se_plane_reduce")
-        gz, gp = torch.empty_like(gs), torch.empty_like(gs)
-        gh = torch.empty((B, Cs), dtype=torch.float32, device=x.device)
-        gw1, gw2 = torch.empty_like(w1), torch.empty_like(w2)
-        gb1 = torch.empty(Cs, dtype=torch.float32, device=x.device)
-        gb2 = torch.empty(C, dtype=torch.float32, device=x.device)
-        _lib.check(lib.ias_se_mlp_backward(_lib.ptr(gs), _lib.ptr(z), _lib.ptr(h), _lib.ptr(pooled), _lib.ptr(w1), _lib.ptr(w2),
-                                           _lib.ptr(gz), _lib.ptr(gh), _lib.ptr(gp), _lib.ptr(gw1), _lib.ptr(gb1), _lib.ptr(gw2),
-                                           _lib.ptr(gb2), B, C, Cs, _lib.stream()), "ias_se_mlp_backward")
-        gx = torch.empty_like(x)
-        _lib.check(lib.ias_se_scale(_lib.ptr(gy), _lib.ptr(s), _lib.ptr(gp), _lib.ptr(gx), B * C, hw, 1.0 / hw, _lib.stream()),
-                   "ias_se_scale")
-        return gx, gw1, gb1, gw2, gb2, None
+        return (*_gate_backward(gy.contiguous(), *ctx.saved_tensors), None)
 
 
 class _SEProjFn(torch.autograd.Function):
     """y = W (x * s), s = hardsigmoid(fc2(relu(fc1(mean_hw x)))): a SqueezeExcitation block AND the bias-free 1x1 projection
     behind it (torchvision InvertedResidual) as one node.  The gate is applied by the projection on load
-    (ias_pwconv_forward_scaled): the forward has no `scale * input` pass over the expanded map; the backward is _SEFn's
+    (ias_pwconv_forward with a scale): the forward has no `scale * input` pass over the expanded map; the backward is _SEFn's
     with the projection's input gradient as its cotangent, plus the weight gradient on the gated input
-    (ias_pwconv_backward_weight*_scaled).  Same values as SqueezeExcitation followed by PointwiseConv2d."""
+    (ias_pwconv_backward_weight with the scale).  Same values as SqueezeExcitation followed by PointwiseConv2d."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, w, pooled=None):
-        from . import _lib
         lib = _lib.load()
-        x, w = x.contiguous(), w.contiguous()
+        x, w, w1, w2 = x.contiguous(), w.contiguous(), w1.contiguous(), w2.contiguous()
         _lib.require_f32(x, w1, b1, w2, b2, w)
         B, C, H, W = x.shape
-        hw = H * W
-        Cs, Cout = w1.shape[0], w.shape[0]
-        w1, w2 = w1.contiguous(), w2.contiguous()
-        if pooled is None:          # (else: as the layer in front left it behind, BatchNormAct2d.forward(pool=True))
-            pooled = torch.empty((B, C), dtype=torch.float32, device=x.device)
-            _lib.check(lib.ias_se_plane_reduce(_lib.ptr(x), None, _lib.ptr(pooled), B * C, hw, 1.0 / hw, _lib.stream()),
-                       "ias_se_plane_reduce")
-        h = torch.empty((B, Cs), dtype=torch.float32, device=x.device)
-        z, s = torch.empty_like(pooled), torch.empty_like(pooled)
-        _lib.check(lib.ias_se_mlp_forward(_lib.ptr(pooled), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(h),
-                                          _lib.ptr(z), _lib.ptr(s), B, C, Cs, _lib.stream()), "ias_se_mlp_forward")
+        Cout = w.shape[0]
+        pooled, h, z, s = _gate_forward(x, w1, b1, w2, b2, pooled)
         y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-        _lib.check(lib.ias_pwconv_forward_scaled(_lib.ptr(x), _lib.ptr(s), _lib.ptr(w), _lib.ptr(y), B, C, Cout, hw,
-                                                 _lib.stream()), "ias_pwconv_forward_scaled")
+        _lib.check(lib.ias_pwconv_forward(_lib.ptr(x), _lib.ptr(s), _lib.ptr(w), _lib.ptr(y), B, C, Cout, H * W, _lib.stream()),
+                   "ias_pwconv_forward")
         ctx.save_for_backward(x, pooled, h, z, s, w1, w2, w)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
         lib = _lib.load()
         x, pooled, h, z, s, w1, w2, w = ctx.saved_tensors
         g = g.contiguous()
         B, C, H, W = x.shape
         hw = H * W
-        Cs, Cout = w1.shape[0], w.shape[0]
-        # the cotangent of the gated map x * s (_SEFn's backward runs on it below)
+        Cout = w.shape[0]
+        # the cotangent of the gated map x * s (the gate's backward runs on it below)
         gy = torch.empty_like(x)
         _lib.check(lib.ias_pwconv_backward_data(_lib.ptr(g), _lib.ptr(w), _lib.ptr(gy), B, C, Cout, hw, _lib.stream()),
                    "ias_pwconv_backward_data")
@@ -516,31 +489,9 @@ class _SEProjFn(torch.autograd.Function):
         gw = None
         if ctx.needs_input_grad[5]:
             gw = torch.empty_like(w)
-            scratch = torch.empty(int(lib.ias_pwconv_weight_scratch(B, C, Cout, hw)), dtype=torch.float32, device=x.device)
-            if _DEFER["on"]:
-                rows = lib.ias_pwconv_backward_weight_partials_scaled(_lib.ptr(g), _lib.ptr(x), _lib.ptr(s), _lib.ptr(scratch),
-                                                                      B, C, Cout, hw, _lib.stream())
-                _lib.check(min(int(rows), 0), "ias_pwconv_backward_weight_partials_scaled")
-                _defer_reduction(scratch, gw, gw.numel(), rows)
-            else:
-                _lib.check(lib.ias_pwconv_backward_weight_scaled(_lib.ptr(g), _lib.ptr(x), _lib.ptr(s), _lib.ptr(gw),
-                                                                 _lib.ptr(scratch), B, C, Cout, hw, _lib.stream()),
-                           "ias_pwconv_backward_weight_scaled")
-        gs = torch.empty((B, C), dtype=torch.float32, device=x.device)
-        _lib.check(lib.ias_se_plane_reduce(_lib.ptr(gy), _lib.ptr(x), _lib.ptr(gs), B * C, hw, 1.0, _lib.stream()),
-                   "ias_se_plane_reduce")
-        gz, gp = torch.empty_like(gs), torch.empty_like(gs)
-        gh = torch.empty((B, Cs), dtype=torch.float32, device=x.device)
-        gw1, gw2 = torch.empty_like(w1), torch.empty_like(w2)
-        gb1 = torch.empty(Cs, dtype=torch.float32, device=x.device)
-        gb2 = torch.empty(C, dtype=torch.float32, device=x.device)
-        _lib.check(lib.ias_se_mlp_backward(_lib.ptr(gs), _lib.ptr(z), _lib.ptr(h), _lib.ptr(pooled), _lib.ptr(w1), _lib.ptr(w2),
-                                           _lib.ptr(gz), _lib.ptr(gh), _lib.ptr(gp), _lib.ptr(gw1), _lib.ptr(gb1), _lib.ptr(gw2),
-                                           _lib.ptr(gb2), B, C, Cs, _lib.stream()), "ias_se_mlp_backward")
-        gx = torch.empty_like(x)
-        _lib.check(lib.ias_se_scale(_lib.ptr(gy), _lib.ptr(s), _lib.ptr(gp), _lib.ptr(gx), B * C, hw, 1.0 / hw, _lib.stream()),
-                   "ias_se_scale")
-        return gx, gw1, gb1, gw2, gb2, gw, None
+            weight_gradient(lib.ias_pwconv_backward_weight, lib.ias_pwconv_weight_scratch(B, C, Cout, hw), gw, (g, x, s),
+                            B, C, Cout, hw)
+        return (*_gate_backward(gy, x, pooled, h, z, s, w1, w2), gw, None)
 
 
 FUSE_SE_PROJECTION = True      # (tests / scripts/diag A/B runs: False keeps SqueezeExcitation and its projection apart)

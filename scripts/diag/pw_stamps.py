@@ -29,7 +29,7 @@ for ci, co, hw in [(240, 40, 240), (40, 240, 240), (96, 40, 240), (144, 48, 240)
     w = torch.randn(co, ci, device=dev)
     y = torch.empty(B, co, hw, device=dev)
     big = torch.empty(64 << 20, device=dev)                     # 256 MB: pushes x out of the Infinity Cache between calls
-    fn = lambda: lib.ias_pwconv_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(y), B, ci, co, hw, st)
+    fn = lambda: lib.ias_pwconv_forward(_lib.ptr(x), None, _lib.ptr(w), _lib.ptr(y), B, ci, co, hw, st)
     for _ in range(2):
         fn()
     big.zero_()

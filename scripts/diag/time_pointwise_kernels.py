@@ -34,9 +34,9 @@ def main():
         w = torch.randn(co, ci, device=dev)
         y, gx, gw = torch.empty_like(g), torch.empty_like(x), torch.empty_like(w)
         scratch = torch.empty(int(lib.ias_pwconv_weight_scratch(B, ci, co, hw)), device=dev)
-        t = [timed(lambda: lib.ias_pwconv_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(y), B, ci, co, hw, st)),
+        t = [timed(lambda: lib.ias_pwconv_forward(_lib.ptr(x), None, _lib.ptr(w), _lib.ptr(y), B, ci, co, hw, st)),
              timed(lambda: lib.ias_pwconv_backward_data(_lib.ptr(g), _lib.ptr(w), _lib.ptr(gx), B, ci, co, hw, st)),
-             timed(lambda: lib.ias_pwconv_backward_weight(_lib.ptr(g), _lib.ptr(x), _lib.ptr(gw), _lib.ptr(scratch), B, ci, co, hw, st))]
+             timed(lambda: lib.ias_pwconv_backward_weight(_lib.ptr(g), _lib.ptr(x), None, _lib.ptr(gw), _lib.ptr(scratch), B, ci, co, hw, st))]
         mb = (x.numel() + g.numel()) * 4 / 1e6
         for i in range(3):
             tot[i] += t[i]

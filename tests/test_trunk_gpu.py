@@ -282,7 +282,7 @@ def test_pointwise_conv_matches_torch(lib, dev, B, Cin, Cout, H, W):
                                    (3, 24, 30, 31)])
 @pytest.mark.parametrize("act", [None, torch.nn.Hardswish])
 def test_batchnorm_leaves_the_squeeze_excitation_pool_behind(lib, dev, shape, act):
-    """BatchNormAct2d.forward(x, pool=True) (ias_bn_act_forward_pool: the following squeeze-excitation block's average pool
+    """BatchNormAct2d.forward(x, pool=True) (ias_bn_act_forward with `pooled`: the following squeeze-excitation block's average pool
     from the normalisation's own launch on maps up to 15 x 16, ias_se_plane_reduce behind it on larger ones): the same y
     and the same gradients as the plain forward, pooled = y.mean((2, 3)), not differentiable; and an inverted-residual
     block that hands the pool on against the same block with the pool computed by the gate itself."""
@@ -337,7 +337,7 @@ def test_inverted_residual_hands_the_pool_to_its_gate(lib, dev):
                                              (3, 120, 32, 48, 15, 16), (130, 144, 40, 48, 15, 16), (3, 24, 8, 8, 5, 7),
                                              (2, 288, 72, 96, 8, 8)])      # the last: the projection's batched-GEMM form
 def test_squeeze_excitation_gate_taken_by_the_projection_on_load(lib, dev, B, C, Cs, Cout, H, W):
-    """vision.se_projection (_SEProjFn: ias_pwconv_forward_scaled / ias_pwconv_backward_weight_scaled, no `scale * input`
+    """vision.se_projection (_SEProjFn: ias_pwconv_forward / ias_pwconv_backward_weight with a scale, no `scale * input`
     pass) against SqueezeExcitation followed by PointwiseConv2d: the same bits forward and for every gradient that does not
     pass through the weight-gradient sums, the projection's weight gradient against fp64 (and, where the fused node runs,
     the same bits twice and through the deferred joint reduction)."""
@@ -378,7 +378,7 @@ def test_squeeze_excitation_gate_taken_by_the_projection_on_load(lib, dev, B, C,
 
 @pytest.mark.parametrize("shape", [(128, 40, 15, 16), (6, 24, 30, 31), (3, 96, 8, 8), (2, 33, 7, 9), (128, 24, 30, 31)])
 def test_batchnorm_with_the_residual_in_the_same_pass(lib, dev, shape):
-    """BatchNormAct2d.forward(x, residual=r) (ias_bn_act_forward_res: the skip connection of an inverted-residual block
+    """BatchNormAct2d.forward(x, residual=r) (ias_bn_act_forward with `res`: the skip connection of an inverted-residual block
     added by the block's last normalisation) against the separate addition: the same bits forward, the same gradients for
     x, the residual and the affine parameters -- on the one-workgroup-per-channel kernels (maps up to 15 x 16), the
     three-launch form (30 x 31) and the scalar form (odd sizes)."""
@@ -474,3 +474,80 @@ def test_reduce_partials_multi_through_the_c_abi(lib, dev):
     table[3].rows = 0
     assert lib.ias_reduce_partials_multi(ctypes.cast(table, ctypes.c_void_p), len(shapes), _lib.stream()) == -1
     assert lib.ias_reduce_partials_multi(None, 3, _lib.stream()) == -1
+
+
+def test_merged_entries_refuse_bad_arguments_before_any_launch(lib, dev):
+    """The entries that took over their siblings' variants through nullable pointers: ias_bn_act_forward with BOTH `res`
+    and `pooled` (no layer has both), ias_pwconv_backward_weight without scratch, ias_colsum on zero rows -> IAS_ERR_ARG,
+    and nothing was launched: every output still holds what it held."""
+    from inverse_audio_synthesis_amd import _lib
+    p, st = _lib.ptr, _lib.stream()
+    B, C, HW = 2, 32, 16
+    x, res = randn((B, C, HW), 1).to(dev), randn((B, C, HW), 2).to(dev)
+    w, b, rm, rv = torch.ones(C, device=dev), torch.zeros(C, device=dev), torch.zeros(C, device=dev), torch.ones(C, device=dev)
+    y, pooled = torch.full((B, C, HW), 7.0, device=dev), torch.full((B, C), 7.0, device=dev)
+    mean, invstd = torch.full((C,), 7.0, device=dev), torch.full((C,), 7.0, device=dev)
+    scratch = torch.empty(int(lib.ias_bn_scratch_doubles(B, C)), dtype=torch.float64, device=dev)
+    assert lib.ias_bn_act_forward(p(x), p(res), p(w), p(b), p(rm), p(rv), p(y), p(pooled), p(mean), p(invstd), p(scratch), B, C, HW,
+                                  1e-3, 0.01, 2, st) == -1
+    Cin, Cout = 16, 24
+    g, xi = randn((B, Cout, HW), 3).to(dev), randn((B, Cin, HW), 4).to(dev)
+    gw = torch.full((Cout, Cin), 7.0, device=dev)
+    assert lib.ias_pwconv_backward_weight(p(g), p(xi), None, p(gw), None, B, Cin, Cout, HW, st) == -1
+    a, out = randn((8, 32), 5).to(dev), torch.full((32,), 7.0, device=dev)
+    cs = torch.full((int(lib.ias_colsum_scratch_floats(8, 32)),), 7.0, device=dev)
+    assert lib.ias_colsum(p(a), p(out), p(cs), 0, 32, st) == -1
+    torch.cuda.synchronize()
+    for t in (y, pooled, mean, invstd, gw, out, cs):
+        assert bool((t == 7.0).all())
+    assert bool((rm == 0.0).all()) and bool((rv == 1.0).all())
+
+
+def test_reduction_entries_agree_with_and_without_their_own_reduction(lib, dev):
+    """ias_pwconv_backward_weight (plain and with a scale), ias_dwconv_backward_weight, ias_stem_backward_weight and
+    ias_colsum through the C ABI, once with the gradient pointer and once with NULL into a second scratch: the same number
+    r >= 2 of partial rows, the same bits in them, and ias_reduce_partials_multi over the NULL form's rows gives the
+    gradient -- bit-equal for the 1x1 and the column sums (the same order of additions), within 1e-6 of the largest
+    element for depthwise and stem (another fixed order; the bound of
+    test_deferred_weight_gradient_reductions_equal_the_immediate_ones)."""
+    import ctypes
+    from inverse_audio_synthesis_amd import _lib
+    from inverse_audio_synthesis_amd.vision import _ReduceItem
+    st = _lib.stream()
+    t = lambda shape, seed: randn(shape, seed).to(dev)
+    B, Cin, Cout, HW = 2, 16, 24, 60 * 62
+    C, K, S, H, W = 16, 3, 2, 30, 31
+    Ho, Wo = lib.ias_conv_out_size(H, K, S), lib.ias_conv_out_size(W, K, S)
+    sH, sW = 24, 25
+    pw_floats, pw_g, pw_x = lib.ias_pwconv_weight_scratch(B, Cin, Cout, HW), t((B, Cout, HW), 1), t((B, Cin, HW), 2)
+    # name: (entry, scratch floats, input tensors (None: no scale), dims, gradient elements, bit-equal)
+    cases = {
+        "pwconv": (lib.ias_pwconv_backward_weight, pw_floats, (pw_g, pw_x, None), (B, Cin, Cout, HW), Cout * Cin, True),
+        "pwconv scaled": (lib.ias_pwconv_backward_weight, pw_floats, (pw_g, pw_x, t((B, Cin), 3)), (B, Cin, Cout, HW),
+                          Cout * Cin, True),
+        "dwconv": (lib.ias_dwconv_backward_weight, lib.ias_dwconv_weight_scratch_hw(B, C, H, W, K, S),
+                   (t((B, C, H, W), 4), t((B, C, Ho, Wo), 5)), (B, C, H, W, K, S), C * K * K, False),
+        "stem": (lib.ias_stem_backward_weight, lib.ias_stem_weight_scratch(B),
+                 (t((B, 3, sH, sW), 6), t((B, 16, lib.ias_conv_out_size(sH, 3, 2), lib.ias_conv_out_size(sW, 3, 2)), 7)),
+                 (B, sH, sW), 432, False),
+        "colsum": (lib.ias_colsum, lib.ias_colsum_scratch_floats(2 * 7 * 7, 32), (t((2 * 7 * 7, 32), 8),), (2 * 7 * 7, 32), 32, True),
+    }
+    for name, (entry, floats, inputs, dims, n, exact) in cases.items():
+        ptrs = [_lib.ptr(a) for a in inputs]
+        s1, s2 = torch.full((int(floats),), float("nan"), device=dev), torch.full((int(floats),), -3.0, device=dev)
+        g1, g2 = torch.full((n,), float("nan"), device=dev), torch.full((n,), float("nan"), device=dev)
+        r = entry(*ptrs, _lib.ptr(g1), _lib.ptr(s1), *dims, st)
+        assert r >= 2, (name, r)
+        assert entry(*ptrs, None, _lib.ptr(s2), *dims, st) == r, name
+        assert r * n <= int(floats), (name, r, n, floats)
+        item = _ReduceItem(s2.data_ptr(), g2.data_ptr(), n, r)
+        assert lib.ias_reduce_partials_multi(ctypes.cast(ctypes.pointer(item), ctypes.c_void_p), 1, st) == 0, name
+        torch.cuda.synchronize()
+        assert torch.equal(s1[:r * n], s2[:r * n]), name
+        assert bool(torch.isfinite(g1).all()), name
+        if exact:
+            assert torch.equal(g1, g2), name
+        else:
+            err, scale = (g1 - g2).abs().max().item(), max(1e-6, g1.abs().max().item())
+            print(f"{name}: rows {r}, max |difference| {err:.3e}, largest element {scale:.3e}")
+            assert err <= 1e-6 * scale, (name, err, scale)
