@@ -120,7 +120,12 @@ int ias_pqmf_out_len(int T, int N, int K);
  * expression.
  * stage -1: everything.  0 / 1: in two stages on the same buffers: stage 0 = the phase increments and their tile sums
  * from the control signals (no cotangent: g_mixed, rownorm, noise, partials, g_ctrl, g_scal may be NULL), stage 1 =
- * everything else.  Any other stage: IAS_ERR_ARG. */
+ * everything else.  Any other stage: IAS_ERR_ARG.
+ * ias_voice_backward_form(T, Tc): which of its two kernel families ias_voice_backward runs at this shape, decided by the
+ * code the call itself uses (host only, no launch): 0 = the lane-consecutive ("fold") kernels, 1 = the first form (chunk
+ * scans and a separate transposed upsample, taken when the per-tile interval sums do not fit the spare plane), or
+ * IAS_ERR_ARG / IAS_ERR_UNSUPPORTED as the call would return. */
+int ias_voice_backward_form(int T, int Tc);
 int ias_voice_grad_tiles(int T);
 int ias_voice_grad_nscalars(void);
 int ias_voice_grad_nplanes(void);

@@ -950,6 +950,36 @@ extern "C" int ias_voice_grad_tiles(int T) { return T > 0 ? (T + GRAD_TILE - 1) 
 extern "C" int ias_voice_grad_nscalars(void) { return IAS_GRAD_NS; }
 extern "C" int ias_voice_grad_nplanes(void) { return IAS_GRAD_PLANES; }
 
+// Which kernel family a row of T samples with Tc control points takes, and the launch figures that go with it.
+struct VoiceGradPlan {
+  int form;       // 0: lane-consecutive ("fold") kernels, 1: first form (chunk scans + separate transposed upsample)
+  int ntiles, kslots, nint;
+  float scale;
+};
+static int voice_grad_plan(int T, int Tc, VoiceGradPlan& pl) {
+  if (T <= 1 || Tc <= 1) return IAS_ERR_ARG;
+  pl.ntiles = (T + GRAD_TILE - 1) / GRAD_TILE;
+  if (pl.ntiles > 65535) return IAS_ERR_UNSUPPORTED;
+  pl.scale = (float)(Tc - 1) / (float)(T - 1);
+  // lane-consecutive form: >= G16_SPT samples per control interval and the per-tile interval sums fit the spare plane
+  pl.kslots = (int)(pl.scale * (float)GRAD_TILE) + 3;
+  const bool fold = pl.scale * (float)G16_SPT <= 1.0f && !voice_grad_force_v1() &&
+                    (size_t)pl.ntiles * IAS_NCTRL * pl.kslots * 2 * sizeof(double) + 8 <= (size_t)T * sizeof(float);
+  // first form: K3 stages nint + 1 control intervals of samples in LDS (as many as fit, at most CT_INTERVALS) and keeps
+  // its interval sums in the spare plane
+  pl.nint = min(CT_INTERVALS, (int)((double)CT_CAP / ((double)(T - 1) / (double)(Tc - 1) + 2.0)) - 1);
+  if (!fold && (pl.nint < 1 || (size_t)IAS_NCTRL * Tc * 2 * sizeof(double) + 8 > (size_t)T * sizeof(float)))
+    return IAS_ERR_UNSUPPORTED;
+  pl.form = fold ? 0 : 1;
+  return IAS_OK;
+}
+// 0 / 1: the form ias_voice_backward runs at this shape (host only, no launch), or a negative error
+extern "C" int ias_voice_backward_form(int T, int Tc) {
+  VoiceGradPlan pl;
+  const int st = voice_grad_plan(T, Tc, pl);
+  return st == IAS_OK ? pl.form : st;
+}
+
 // rownorm [B][4] from the cotangent g [B,T] of the NORMALISED audio [B,T] and the row peaks of the un-normalised mix
 // (ias_voice_read_peaks); scratch: ias_voice_norm_scratch_len(T) * B doubles.  Feed rownorm and g to
 // ias_voice_backward: the division by the peak and the correction at the peak sample happen as g is read.
@@ -991,18 +1021,12 @@ extern "C" int ias_voice_backward(int stage, const float* ctrl, const void* vcon
   if (!ctrl || !vconst || !planes || !tile_sums) return IAS_ERR_ARG;
   if (stage != 0 && (!noise || !g_mixed || !partials || !g_ctrl)) return IAS_ERR_ARG;
   if (B <= 0 || B > 65535 || T <= 1 || Tc <= 1 || sample_rate <= 0) return IAS_ERR_ARG;
-  const int ntiles = (T + GRAD_TILE - 1) / GRAD_TILE;
-  if (ntiles > 65535) return IAS_ERR_UNSUPPORTED;
-  const float scale = (float)(Tc - 1) / (float)(T - 1);
-  // lane-consecutive form: >= G16_SPT samples per control interval and the per-tile interval sums fit the spare plane
-  const int kslots = (int)(scale * (float)GRAD_TILE) + 3;
-  const bool fold = scale * (float)G16_SPT <= 1.0f && !voice_grad_force_v1() &&
-                    (size_t)ntiles * IAS_NCTRL * kslots * 2 * sizeof(double) + 8 <= (size_t)T * sizeof(float);
-  // first form: K3 stages nint + 1 control intervals of samples in LDS (as many as fit, at most CT_INTERVALS) and keeps
-  // its interval sums in the spare plane
-  const int nint = min(CT_INTERVALS, (int)((double)CT_CAP / ((double)(T - 1) / (double)(Tc - 1) + 2.0)) - 1);
-  if (!fold && (nint < 1 || (size_t)IAS_NCTRL * Tc * 2 * sizeof(double) + 8 > (size_t)T * sizeof(float)))
-    return IAS_ERR_UNSUPPORTED;
+  VoiceGradPlan plan;
+  const int plan_st = voice_grad_plan(T, Tc, plan);
+  if (plan_st != IAS_OK) return plan_st;
+  const int ntiles = plan.ntiles, kslots = plan.kslots, nint = plan.nint;
+  const float scale = plan.scale;
+  const bool fold = plan.form == 0;
   const IasVoiceConst* vc = (const IasVoiceConst*)vconst;
   const dim3 grid(ntiles, B), block(GRAD_THREADS);
   if (stage <= 0)

@@ -205,7 +205,8 @@ class _P:
 
 def _ramp(cfg, m, duration, alpha, start=None, inverse=False):
     dur = (duration * cfg.control_rate).unsqueeze(1)
-    rng = torch.arange(cfg.control_buffer_size, dtype=torch.float32)
+    # (in the math's own dtype: an fp32 range made "f64" add EPS to the attack ramp in single precision)
+    rng = torch.arange(cfg.control_buffer_size, dtype=m.dtype)
     ramp = rng.expand(duration.shape[0], -1)
     if start is not None:
         ramp = ramp - (start * cfg.control_rate).unsqueeze(1)
