@@ -300,6 +300,11 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES == 10 ? 5 : 1) void stft_ke
   const cpx* t_tw1 = t_win + 64 * R;        // [k1]   -> W_N2^(lane k1)
   const cpx* t_tw2 = t_tw1 + 64 * R;        // [8i+d] -> W_64^(c d)
   const cpx* t_twu = t_tw2 + 64 * 8 * NP_IT;  // [i]  -> W_NFFT^(lane + 64 i)
+  // The padded filter loops of the epilogue read up to three words past the N2 + 1 power values of the wave's scratch.
+  // Where such a word is a slot of the FFT passes it holds a stale, finite value by then; where it is a padding slot
+  // nothing ever writes it (n_fft 2048: word N2 + 1 is the second half of complex slot 512 = 56 * 9 + 8), and a zero
+  // weight times whatever bits the LDS held is NaN when they happen to spell one.  Zeroed once: padding slots keep it.
+  if (mel && lane < 3) reinterpret_cast<float*>(s_scr + wave * SCR)[N2 + 1 + lane] = 0.0f;
   __syncthreads();   // mel tables visible; the only workgroup barrier before the final reduction
 
   cpx* sA = s_scr + wave * SCR;
@@ -445,7 +450,8 @@ __global__ __launch_bounds__(64 * SP_WAVES, SP_WAVES == 10 ? 5 : 1) void stft_ke
             }
           }
           // (na, nb, nmaxa, nmaxb are multiples of four; a lane whose filter has ended re-reads its first trip and
-          //  keeps its sum; the zero padding multiplies power values of neighbouring bins, which are finite.)
+          //  keeps its sum; the zero padding multiplies power values of neighbouring bins, or up to three scratch words
+          //  behind the last bin: all finite, see the zeroing in front of the frame loop.)
           // Measured alternatives that were slower: one merged loop advancing both chains with the next trip's reads
           // issued ahead (94.7 vs 84.9 us: the short chain then re-reads for the long chain's trips and the LDS is the
           // co-bottleneck), 10 waves per workgroup at 5 waves per SIMD (98.9 us).
@@ -1168,6 +1174,9 @@ __global__ __launch_bounds__(256) void stft_grad_wave_kernel(const SgwArgs a) {
   const cpx* t_tw1 = t_win + 64 * R;
   const cpx* t_tw2 = t_tw1 + 64 * R;
   const cpx* t_twu = t_tw2 + 64 * 8 * NP_IT;
+  // the padded filter loop reads up to three words past the NB values V of the wave's scratch: zeroed once, as in
+  // stft_kernel (n_fft 512: words NB and NB + 1 .. 2 lie in the padding columns of row 12, which no pass writes)
+  if (MEL && lane < 3) reinterpret_cast<float*>(s_scr + wave * SCR)[NB + lane] = 0.0f;
   __syncthreads();
   cpx* sA = s_scr + wave * SCR;
   float c0 = 0.0f, c1 = 0.0f;
