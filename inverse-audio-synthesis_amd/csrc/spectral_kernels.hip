@@ -77,6 +77,11 @@ __device__ __forceinline__ cpx cnegi_sub(cpx x, cpx a) {    // (-i) x - a = (x.y
 }
 #endif
 
+// a * (1, -0): W^0 as the twiddle tables hold it (cos 0, -sin 0), without reading it.  cmul's own two results for that
+// operand -- a.x * 1 is a.x, and (-a.y)(-0) = a.y * 0, a.x * (-0) = (-a.x) * 0 with their signs -- so the same bits, zeros
+// included; the zero is an inline constant and the signs are source modifiers: two instructions, no register.
+__device__ __forceinline__ cpx cmul_unit(cpx a) { return cmk(__builtin_fmaf(a.y, 0.0f, a.x), __builtin_fmaf(-a.x, 0.0f, a.y)); }
+
 // forward DFTs (kernel e^{-2 pi i nk/R}), in place, natural order.  A multiplication by -i is never materialised: the
 // add or subtract that consumes it takes the swap and the sign.
 __device__ __forceinline__ void dft4(cpx& v0, cpx& v1, cpx& v2, cpx& v3) {
@@ -658,26 +663,73 @@ void stft2_kernel(const Spec2Args a) {
   __shared__ int s_sega[MEL ? 9 * 64 : 1];                          // MEL: [9][64] store offsets
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int gw = blockIdx.x * SP_WAVES + wave, nw = gridDim.x * SP_WAVES;
+
+  auto row_of = [&](int fi, int& b, int& f) {
+    unsigned q0 = __umulhi((unsigned)fi, a.magicF);
+    int r = fi - (int)q0 * a.F;
+    if (r >= a.F) { r -= a.F; ++q0; }
+    b = (int)q0; f = r;
+  };
+  // n_fft 1024: ONE set of frame registers -- the loop loads a wave's next frame into xc once pass 1's radix-8 step has
+  // consumed the current one.  n_fft 2048 keeps a second set, loaded at the top of the loop and copied at its end: loaded in the middle
+  // of its frame, beside the first half-transform's results, the 32 addresses of a row-end frame take it from 148-150
+  // VGPRs to 168 and 20-32 bytes of scratch.
+  // The first frame and its row peak are requested here, ahead of the table staging and the workgroup barrier, which
+  // their way from HBM overlaps.  The row peak travels with the frame's samples: read where it is used, its wait -- the
+  // memory counter is in order -- would drain the prefetch of the next frame in every iteration.
+  constexpr bool ONESET = NSUB == 1;
+  float xc[16 * NSUB], xn[ONESET ? 1 : 16 * NSUB];
+  int fi = gw;
+  float pk_cur = 0.0f, pk_next = 0.0f;
+  if (fi < a.nframes) {
+    int b0, f0;
+    row_of(fi, b0, f0);
+    stft2_load_frame<NSUB>(a.audio + (size_t)b0 * a.T, a.T, a.hop, f0, lane, xc);
+    if (a.rowpeak != nullptr) pk_cur = a.rowpeak[b0];
+  }
 
   // tables.  n_fft 1024: the old block's entries [0,16) window, [16,32) pass-1, [32,48) pass-2 twiddles, and this
   // kernel's unpack twiddles W_1024^k, k = (lane >> 3) + 8 (lane & 7) + 64 e, in the 8 entries behind the old block's
   // unpack entries.  n_fft 2048: this kernel's own section behind the old block (ias_stft_build_tables), in s_tab order.
   constexpr int OLD_UNP = 10, V2_BASE_2048 = 32 + 32 + 32 + 18;
-  for (int i = tid; i < NTAB * 64; i += SP_THREADS) {
-    const int pp = i >> 6, l = i & 63;
-    const int src = NSUB == 2 ? V2_BASE_2048 + 2 * pp : (pp < 24 ? 2 * pp : 48 + OLD_UNP + 2 * (pp - 24));
-    s_tab[i] = cmk(a.tables[64 * src + l], a.tables[64 * (src + 1) + l]);
+  auto tab_src = [&](int i) {
+    const int pp = i >> 6;
+    return 64 * (NSUB == 2 ? V2_BASE_2048 + 2 * pp : (pp < 24 ? 2 * pp : 48 + OLD_UNP + 2 * (pp - 24))) + (i & 63);
+  };
+  int seg_rows = 0, seg_r[3] = {0, 0, 0}, seg_s0 = 0;
+  const int* hdr = reinterpret_cast<const int*>(a.segtab);
+  const cpx* wsrc = reinterpret_cast<const cpx*>(a.segtab + IAS_SEG_HDR + 9 * 64);
+  if (MEL) { seg_rows = hdr[1]; seg_r[0] = hdr[2]; seg_r[1] = hdr[3]; seg_r[2] = hdr[4]; seg_s0 = hdr[5]; }
+  // Every global load of the staging is issued before the first LDS store waits for one: a thread's 3-4 table entries,
+  // 1-2 store offsets and 2-3 weight pairs are ONE trip to memory.  As loops of load / wait / store they were 9-10 trips
+  // in a row, in all workgroups at once at the start of the launch, when no wave has a frame to transform yet.
+  constexpr int TAB_IT = (NTAB * 64 + SP_THREADS - 1) / SP_THREADS, SEGA_IT = (9 * 64 + SP_THREADS - 1) / SP_THREADS;
+  constexpr int SEGW_IT = (IAS_SEG_MAX_ROWS * 64 + SP_THREADS - 1) / SP_THREADS;
+  float st_re[TAB_IT], st_im[TAB_IT];
+  int st_a[MEL ? SEGA_IT : 1];
+  cpx st_w[MEL ? SEGW_IT : 1];
+#pragma unroll
+  for (int k = 0; k < TAB_IT; ++k) {
+    const int i = tid + k * SP_THREADS;
+    if (i < NTAB * 64) { st_re[k] = a.tables[tab_src(i)]; st_im[k] = a.tables[tab_src(i) + 64]; }
+  }
+  if (MEL) {
+#pragma unroll
+    for (int k = 0; k < SEGA_IT; ++k) { const int i = tid + k * SP_THREADS; if (i < 9 * 64) st_a[k] = hdr[IAS_SEG_HDR + i]; }
+#pragma unroll
+    for (int k = 0; k < SEGW_IT; ++k) { const int i = tid + k * SP_THREADS; if (i < seg_rows * 64) st_w[k] = wsrc[i]; }
   }
   // the scratch doubles as the segment-major power buffer, some of whose words (the padding of the exchange layout,
   // positions past the end of a short segment) no pass ever writes: they meet zero weights and must be finite
   for (int i = tid; i < SP_WAVES * SCR; i += SP_THREADS) s_scr[i] = cmk(0.f, 0.f);
-  int seg_rows = 0, seg_r[3] = {0, 0, 0}, seg_s0 = 0;
+#pragma unroll
+  for (int k = 0; k < TAB_IT; ++k) { const int i = tid + k * SP_THREADS; if (i < NTAB * 64) s_tab[i] = cmk(st_re[k], st_im[k]); }
   if (MEL) {
-    const int* hdr = reinterpret_cast<const int*>(a.segtab);
-    seg_rows = hdr[1]; seg_r[0] = hdr[2]; seg_r[1] = hdr[3]; seg_r[2] = hdr[4]; seg_s0 = hdr[5];
-    for (int i = tid; i < 9 * 64; i += SP_THREADS) s_sega[i] = hdr[IAS_SEG_HDR + i];
-    const cpx* wsrc = reinterpret_cast<const cpx*>(a.segtab + IAS_SEG_HDR + 9 * 64);
-    for (int i = tid; i < seg_rows * 64; i += SP_THREADS) s_segw[i] = wsrc[i];
+#pragma unroll
+    for (int k = 0; k < SEGA_IT; ++k) { const int i = tid + k * SP_THREADS; if (i < 9 * 64) s_sega[i] = st_a[k]; }
+#pragma unroll
+    for (int k = 0; k < SEGW_IT; ++k) { const int i = tid + k * SP_THREADS; if (i < seg_rows * 64) s_segw[i] = st_w[k]; }
   }
   const cpx* t_win = s_tab + lane;              // [8 sub + n1] -> the window at the lane's two samples of point n1
   const cpx* t_tw1 = t_win + 64 * 8 * NSUB;     // [k1]  -> W_512^(lane k1)
@@ -690,27 +742,11 @@ void stft2_kernel(const Spec2Args a) {
   float* P2 = reinterpret_cast<float*>(sA);
 
   float l0 = 0.f, l1 = 0.f, l2 = 0.f;
-  const int gw = blockIdx.x * SP_WAVES + wave, nw = gridDim.x * SP_WAVES;
   const int k1 = lane >> 3, dd = lane & 7;   // after the last pass the lane holds Z[k1 + 8 dd + 64 e]
-
-  auto row_of = [&](int fi, int& b, int& f) {
-    unsigned q0 = __umulhi((unsigned)fi, a.magicF);
-    int r = fi - (int)q0 * a.F;
-    if (r >= a.F) { r -= a.F; ++q0; }
-    b = (int)q0; f = r;
-  };
-  float xc[16 * NSUB], xn[16 * NSUB];
 #ifdef IAS_S2_STAMPS
   int stamp_n = 0;
 #endif
-  int fi = gw, bcur = 0, fcur = 0;
-  // the row peak travels with the frame's samples (requested one frame ahead): read where it is used, its wait -- the
-  // memory counter is in order -- would drain the prefetch of the next frame in every iteration
-  float pk_cur = 0.0f, pk_next = 0.0f;
   if (fi < a.nframes) {
-    row_of(fi, bcur, fcur);
-    stft2_load_frame<NSUB>(a.audio + (size_t)bcur * a.T, a.T, a.hop, fcur, lane, xc);
-    if (a.rowpeak != nullptr) pk_cur = a.rowpeak[bcur];
     // the first frame's loads are consumed HERE, outside the loop: left pending into the loop header they make the
     // compiler wait for "everything older" at the first use inside the body, which is behind the next frame's prefetch in
     // program order -- a full drain of the memory pipeline (vmcnt(0)) in every iteration
@@ -721,10 +757,10 @@ void stft2_kernel(const Spec2Args a) {
   for (; fi < a.nframes; fi += nw) {
     const bool more = fi + nw < a.nframes;   // wave-uniform
     S2_STAMP(1);
-    int bnext = 0, fnext = 0;
-    if (more) {
+    if (!ONESET && more) {
+      int bnext, fnext;
       row_of(fi + nw, bnext, fnext);
-      stft2_load_frame<NSUB>(a.audio + (size_t)bnext * a.T, a.T, a.hop, fnext, lane, xn);
+      stft2_load_frame<NSUB>(a.audio + (size_t)bnext * a.T, a.T, a.hop, fnext, lane, reinterpret_cast<float (&)[16 * NSUB]>(xn));
       if (a.rowpeak != nullptr) pk_next = a.rowpeak[bnext];
     }
     float pscale = 0.25f;
@@ -754,10 +790,25 @@ void stft2_kernel(const Spec2Args a) {
 #pragma unroll
       for (int n1 = 0; n1 < R; ++n1) v[n1] = cmk(xc[16 * sub + 2 * n1], xc[16 * sub + 2 * n1 + 1]) * t_win[64 * (8 * sub + n1)];
       dft8(v);
+      if (ONESET) {
+        // xc is dead behind the transform's first additions, into which the compiler contracts half of the window
+        // products (so the empty statements that keep the loads below from being issued before that, into registers of
+        // their own, take the transform's results: on the products they would undo the contraction and change the rounding).
+        // The next frame goes into xc itself, a whole frame ahead less this radix-8 step.  The frame's target row was
+        // requested above, so waiting for it does not wait for these loads.  The last iteration loads nothing.
+#pragma unroll
+        for (int n1 = 0; n1 < R; ++n1) asm volatile("" : "+v"(v[n1]));
+        if (more) {
+          int bnext, fnext;
+          row_of(fi + nw, bnext, fnext);
+          stft2_load_frame<NSUB>(a.audio + (size_t)bnext * a.T, a.T, a.hop, fnext, lane, xc);
+          if (a.rowpeak != nullptr) pk_cur = a.rowpeak[bnext];
+        }
+      }
       cpx u[8];
 #if IAS_S2_REGX
 #pragma unroll
-      for (int q = 0; q < R; ++q) u[q] = cmul(v[q], t_tw1[64 * q]);
+      for (int q = 0; q < R; ++q) u[q] = q == 0 ? cmul_unit(v[q]) : cmul(v[q], t_tw1[64 * q]);   // entry 0 is W^0 for every lane
       S2_STAMP(2);
       xchg_reg_lane345(u);
       S2_STAMP(3);
@@ -766,7 +817,7 @@ void stft2_kernel(const Spec2Args a) {
       {
         const int c = lane & 7, aa = lane >> 3;
 #pragma unroll
-        for (int q = 0; q < R; ++q) sA[S2X_AT(q * 8 + c, aa)] = cmul(v[q], t_tw1[64 * q]);
+        for (int q = 0; q < R; ++q) sA[S2X_AT(q * 8 + c, aa)] = q == 0 ? cmul_unit(v[q]) : cmul(v[q], t_tw1[64 * q]);
       }
       S2_STAMP(2);
       wave_lds_sync();
@@ -779,7 +830,7 @@ void stft2_kernel(const Spec2Args a) {
       // pass 2: radix 8 over a for each (k1, c); twiddle W_64^(c d); scatter (in place) to [k1][d][c]
       dft8(u);
 #pragma unroll
-      for (int d = 0; d < 8; ++d) sA[S2X_AT(k1 * 8 + d, dd)] = cmul(u[d], t_tw2[64 * d]);
+      for (int d = 0; d < 8; ++d) sA[S2X_AT(k1 * 8 + d, dd)] = d == 0 ? cmul_unit(u[d]) : cmul(u[d], t_tw2[64 * d]);
       S2_STAMP(5);
       wave_lds_sync();
       S2_STAMP(6);
@@ -906,10 +957,10 @@ void stft2_kernel(const Spec2Args a) {
     }
     S2_STAMP(15);
     wave_lds_sync();
-    if (more) {
+    if (!ONESET && more) {
 #pragma unroll
       for (int e = 0; e < 16 * NSUB; ++e) xc[e] = xn[e];
-      bcur = bnext; fcur = fnext; pk_cur = pk_next;
+      pk_cur = pk_next;
     }
   }
 
