@@ -21,7 +21,7 @@ for tagp, name in (("a", "render alone (time_voice.py, eager)"), ("b", "headline
     for f in glob.glob("$O/%s*/**/*counter_collection.csv" % tagp, recursive=True):
         for r in csv.DictReader(open(f)):
             k = r["Kernel_Name"].split("(")[0][:50]
-            if any(x in k for x in ("voice_audio", "stft2_kernel", "pqmf_analysis", "voice_env_slim", "voice_lfo_slim")):
+            if any(x in k for x in ("voice_audio", "stft2_kernel", "pqmf_analysis", "voice_chain_slim", "voice_modmix_slim")):
                 agg[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
     print("==", name)
     for k in sorted(agg):
