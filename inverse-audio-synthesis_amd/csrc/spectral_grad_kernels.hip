@@ -411,7 +411,7 @@ extern "C" int ias_stft_grad_combine(const float* const* spans_host, const int* 
 extern "C" int ias_stft_grad_frames(const float* audio, const float* tables, const int* mel_start, const int* mel_count,
                                     const int* mel_woff, const float* mel_w, int mel_nnz, int n_out, const float* target,
                                     const double* coef, float* frame_grad, int B, int T, int n_fft, int hop, int power,
-                                    int loss_mode, float scale, float eps, void* stream);   // csrc/spectral_kernels.hip
+                                    int loss_mode, float scale, float eps, void* stream);   // csrc/stft_frame_grad_kernels.hip
 extern "C" int ias_stft_grad_spans(const float* audio, const float* tables, const int* mel_start, const int* mel_count,
                                    const int* mel_woff, const float* mel_w, int mel_nnz, int n_out, const float* target,
                                    const double* coef, float* chunk_spans, int B, int T, int n_fft, int hop, int power,

@@ -33,7 +33,7 @@
 // then rows x 64 x (up, down) weights.  Slot i = segment s0 + i lives in group i / 64 (A, B, C) on lane i % 64; row
 // r of group g holds position r - base(g) of the group's segments.
 #define IAS_SEG_MAGIC 0x5e67ab
-#define IAS_SEG_MAX_ROWS 17          // rows x 72 floats fit the wave's 5120-byte FFT scratch (spectral_kernels.hip: IAS_S2_ROW)
+#define IAS_SEG_MAX_ROWS 17          // rows x 72 floats fit the wave's 5120-byte FFT scratch (stft_core.h: IAS_S2_ROW)
 #define IAS_SEG_HDR 16
 #define IAS_SEG_STRIDE 72
 

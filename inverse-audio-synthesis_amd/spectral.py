@@ -1,4 +1,4 @@
-"""STFT / mel spectral losses on the HIP path (csrc/spectral_kernels.hip).
+"""STFT / mel spectral losses on the HIP path (csrc/spectral_kernels.hip; backward: csrc/stft_frame_grad_kernels.hip).
 
 The reference has no live spectral-loss code.  This module implements the spec it left behind:
   * ``MelSpectrogram`` with the argument names/defaults of the commented config block
@@ -9,7 +9,7 @@ The reference has no live spectral-loss code.  This module implements the spec i
     TODO at audio_to_params.py:233; auraloss defaults).
 Filterbank / window / twiddle tables are built once on the host; every per-sample operation runs
 in the HIP kernel.  The L1 losses (``MelSpectrogramL1``, ``STFTL1``) are differentiable with respect to the audio
-(``csrc/spectral_grad_kernels.hip``): with ``Voice.render`` that closes the audio -> params -> synth -> mel-L1 loop
+(``csrc/stft_frame_grad_kernels.hip``, ``csrc/spectral_grad_kernels.hip``): with ``Voice.render`` that closes the audio -> params -> synth -> mel-L1 loop
 the reference left commented out (audio_to_params.py:56-172); ``MultiResolutionSTFTLoss`` is differentiable with
 respect to its first argument (the prediction) through the same kernels.
 """
@@ -477,7 +477,7 @@ class _MRSTFTFn(torch.autograd.Function):
         B, T = a.shape
         g32 = g.to(torch.float32).reshape(B if rows else ()).contiguous()
         eps = float(module.eps)
-        # chunk plans of the fused overlap-add (csrc/spectral_kernels.hip, SPAN kernels)
+        # chunk plans of the fused overlap-add (csrc/stft_frame_grad_kernels.hip, SPAN kernels)
         chunk_plans = []
         for plan in module.plans:
             hp = (ctypes.c_int * 3)()

@@ -1,4 +1,4 @@
-"""Bank-conflict model of the radix-8 kernels' LDS exchanges (csrc/spectral_kernels.hip: IAS_S2_ROW) with the lane groups
+"""Bank-conflict model of the radix-8 kernels' LDS exchanges (csrc/stft_core.h: IAS_S2_ROW) with the lane groups
 and bank moduli of MI355X_MICROARCH.md, section LDS.  Prints the extra LDS cycles per frame of each access pattern for rows
 of 9 and 10 complex values -- the numbers SQ_LDS_BANK_CONFLICT / frames reports for the kernel without its mel part
 (56 and 40).  CPU only: python scripts/diag/lds_exchange_model.py"""

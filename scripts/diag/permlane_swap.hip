@@ -1,5 +1,5 @@
 // What v_permlane32_swap / v_permlane16_swap and the bank-masked DPP row moves do on gfx950, lane by lane, and the
-// register <-> lane-bits transpose built from them (the FFT exchange of csrc/spectral_kernels.hip) against the same
+// register <-> lane-bits transpose built from them (the FFT exchange of csrc/stft_core.h) against the same
 // transpose through LDS.  hipcc --offload-arch=gfx950 -O3 permlane_swap.hip -o permlane_swap
 #include <cstdio>
 #include <hip/hip_runtime.h>

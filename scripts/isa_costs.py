@@ -26,9 +26,9 @@ KERNELS = [  # (json key = the name bench.py / rocprofv3 use, source, extra flag
     ("stft2_kernel<8, false, 2, 1>", "spectral_kernels.hip", ["-fno-slp-vectorize"], "stft2_kernelILi8ELb0ELi2ELi1E"),
     ("stft2_kernel<8, false, 2, 2>", "spectral_kernels.hip", ["-fno-slp-vectorize"], "stft2_kernelILi8ELb0ELi2ELi2E"),
     ("stft2h_kernel<8, 2>", "spectral_kernels.hip", ["-fno-slp-vectorize"], "stft2h_kernelILi8ELi2E"),
-    ("stft_grad_wave_kernel<10, false, true>", "spectral_kernels.hip", ["-fno-slp-vectorize"], "stft_grad_wave_kernelILi10ELb0ELb1ELb0E"),
-    ("stft_grad2k_kernel<8, true>", "spectral_kernels.hip", ["-fno-slp-vectorize"], "stft_grad2k_kernelILi8ELb1ELb0E"),
-    ("stft_grad512_kernel<8>", "spectral_kernels.hip", ["-fno-slp-vectorize"], "stft_grad512_kernelILi8ELb0E"),
+    ("stft_grad_wave_kernel<10, false, true>", "stft_frame_grad_kernels.hip", ["-fno-slp-vectorize"], "stft_grad_wave_kernelILi10ELb0ELb1ELb0E"),
+    ("stft_grad2k_kernel<8, true>", "stft_frame_grad_kernels.hip", ["-fno-slp-vectorize"], "stft_grad2k_kernelILi8ELb1ELb0E"),
+    ("stft_grad512_kernel<8>", "stft_frame_grad_kernels.hip", ["-fno-slp-vectorize"], "stft_grad512_kernelILi8ELb0E"),
     ("voice_grad_sample16_kernel", "voice_grad_kernels.hip", ["-ffp-contract=off", "-fno-slp-vectorize"], "voice_grad_sample16_kernel"),
     ("voice_grad_pitch16_kernel", "voice_grad_kernels.hip", ["-ffp-contract=off", "-fno-slp-vectorize"], "voice_grad_pitch16_kernel"),
     ("pqmf_analysis_mfma_kernel<64, 63, 1, 2, 6>", "pqmf_kernels.hip", ["-fno-slp-vectorize"], "pqmf_analysis_mfma_kernelILi64ELi63ELi1ELi2ELi6E"),

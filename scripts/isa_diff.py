@@ -2,12 +2,16 @@
 """Which kernels does a change to csrc/ touch?  Compiles every *_kernels.hip of two csrc directories to gfx950 assembly
 (device only, the flags csrc/Makefile of that side gives the file) and compares them kernel by kernel:
     python scripts/isa_diff.py <csrc dir A> <csrc dir B> [--diag]        (--diag: the diagnostic library, -DIAS_DIAG)
-Per file: the kernels only A or only B has, the number whose code is identical, and for every kernel that differs the
-VGPR / SGPR / scratch / LDS figures of both sides from the code objects' metadata.  A kernel's text is its function (from
-its `.type ...,@function` to the `.Lfunc_end` label) and its `.amdhsa_kernel` descriptor, without comments and with the
-function index taken out of the local labels (.LBB<n>_<k>), which shifts whenever a kernel in front of it comes or goes.
+Kernels are matched by symbol across all files of a side, so one that moved to another file is compared like any other
+(and listed as moved); reported under the file B has it in: the kernels only A or only B has, the number whose code is
+identical, and for every kernel that differs the VGPR / SGPR / scratch / LDS figures of both sides from the code objects'
+metadata and whether the multiset of its instruction mnemonics is equal (then only registers or the order differ).  A
+kernel's text is its function (from its `.type ...,@function` to the `.Lfunc_end` label) and its `.amdhsa_kernel`
+descriptor, without comments and with the function index taken out of the local labels (.LBB<n>_<k>), which shifts
+whenever a kernel in front of it comes or goes.
 Exit status 1 if a kernel both sides have differs.  Needs hipcc only (no GPU)."""
 import argparse
+import collections
 import concurrent.futures
 import glob
 import os
@@ -77,6 +81,16 @@ def kernels_of(asm):
     return out
 
 
+def mnemonics(text):
+    """Counter of the instruction mnemonics of a kernel's normalised text (labels and directives left out)"""
+    c = collections.Counter()
+    for l in text.split("\n"):
+        t = l.strip()
+        if l.startswith("\t") and t and t[0] != "." and not t.endswith(":"):
+            c[t.split()[0]] += 1
+    return c
+
+
 def demangle(names):
     tool = shutil.which("llvm-cxxfilt", path="/opt/rocm/llvm/bin") or shutil.which("c++filt")
     if not tool or not names:
@@ -97,24 +111,37 @@ def main():
     with tempfile.TemporaryDirectory() as td, concurrent.futures.ThreadPoolExecutor(max(1, min(args.jobs, 16))) as pool:
         jobs = {(f, i): pool.submit(compile_asm, d, f, args.diag, os.path.join(td, f"{i}_{f}.s"))
                 for f in files for i, d in enumerate(dirs) if os.path.exists(os.path.join(d, f))}
-        total = {"only_a": 0, "only_b": 0, "same": 0, "diff": 0}
+        sides = [{}, {}]                                   # symbol -> (file, text, figures)
+        for (f, i), job in sorted(jobs.items()):
+            for sym, (text, figs) in kernels_of(job.result()).items():
+                sides[i][sym] = (f, text, figs)
+        ka, kb = sides
+        total = {"only_a": 0, "only_b": 0, "same": 0, "diff": 0, "moved": 0}
         for f in files:
-            ka, kb = (kernels_of(jobs[(f, i)].result()) if (f, i) in jobs else {} for i in (0, 1))
-            only_a, only_b = sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka))
-            both = sorted(set(ka) & set(kb))
-            diff = [k for k in both if ka[k][0] != kb[k][0]]
-            name = demangle(only_a + only_b + diff)
-            print(f"{f}: {len(both) - len(diff)} identical, {len(diff)} different, {len(only_a)} only in A, {len(only_b)} only in B")
+            only_a = sorted(k for k in ka if k not in kb and ka[k][0] == f)
+            only_b = sorted(k for k in kb if k not in ka and kb[k][0] == f)
+            both = sorted(k for k in kb if k in ka and kb[k][0] == f)
+            diff = [k for k in both if ka[k][1] != kb[k][1]]
+            moved = [k for k in both if ka[k][0] != f]
+            name = demangle(only_a + only_b + diff + moved)
+            print(f"{f}: {len(both) - len(diff)} identical, {len(diff)} different, {len(only_a)} only in A, {len(only_b)} only in B"
+                  + (f", {len(moved)} moved here" if moved else ""))
             for k in only_a:
                 print(f"  only in A: {name[k]}")
             for k in only_b:
                 print(f"  only in B: {name[k]}")
+            for k in moved:
+                print(f"  moved from {ka[k][0]} ({'DIFFERENT' if k in diff else 'identical'}): {name[k]}")
             for k in diff:
-                figs = ", ".join(f"{label} {ka[k][1].get(key, '?')} -> {kb[k][1].get(key, '?')}" for key, label in FIGURES)
-                print(f"  DIFFERENT: {name[k]}: {figs}; {ka[k][0].count(chr(10)) + 1} -> {kb[k][0].count(chr(10)) + 1} lines")
-            total["only_a"] += len(only_a); total["only_b"] += len(only_b)
+                figs = ", ".join(f"{label} {ka[k][2].get(key, '?')} -> {kb[k][2].get(key, '?')}" for key, label in FIGURES)
+                ma, mb = mnemonics(ka[k][1]), mnemonics(kb[k][1])
+                mn = "mnemonic multiset equal" if ma == mb else \
+                    "mnemonic multiset DIFFERS (" + ", ".join(f"{m} {ma[m]} -> {mb[m]}" for m in sorted(set(ma) | set(mb)) if ma[m] != mb[m]) + ")"
+                print(f"  DIFFERENT: {name[k]}: {figs}; {ka[k][1].count(chr(10)) + 1} -> {kb[k][1].count(chr(10)) + 1} lines; {mn}")
+            total["only_a"] += len(only_a); total["only_b"] += len(only_b); total["moved"] += len(moved)
             total["same"] += len(both) - len(diff); total["diff"] += len(diff)
-    print(f"total: {total['same']} identical, {total['diff']} different, {total['only_a']} only in A, {total['only_b']} only in B")
+    print(f"total: {total['same']} identical, {total['diff']} different, {total['only_a']} only in A, {total['only_b']} only in B, "
+          f"{total['moved']} moved")
     return 1 if total["diff"] else 0
 
 

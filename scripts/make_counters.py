@@ -16,7 +16,7 @@ PICK = {"pmc_voice.txt": ("voice_audio_kernel", "voice_audio_kernel"),
 
 
 HASHED = ("voice_kernels.hip", "voice_math.h", "voice_trig.h", "wave_ops.h", "voice_exp2_table.h", "stft2_kernels.hip",
-          "spectral_kernels.hip", "pqmf_kernels.hip", "ias_common.h", "Makefile")
+          "spectral_kernels.hip", "stft_core.h", "pqmf_kernels.hip", "ias_common.h", "Makefile")
 
 
 def kernel_sources_sha16(root):

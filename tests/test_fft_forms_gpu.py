@@ -2,7 +2,7 @@
 
 The product library writes every product that takes a swapped or negated operand -- complex multiplies, multiplications
 by -i inside the radix-4 / radix-8 butterflies -- per component, so that no operand pair is built in front of a packed
-instruction (csrc/spectral_kernels.hip: cmul, cadd_negi, csub_negi, cnegi_sub).  The diagnostic library (-DIAS_DIAG)
+instruction (csrc/stft_core.h: cmul, cadd_negi, csub_negi, cnegi_sub).  The diagnostic library (-DIAS_DIAG)
 keeps the generic 2-wide vector expressions.  Both are the same products, the same fused multiply-adds and the same
 rounding points, so every kernel built on them must give the same bits from either library: the forward transforms of
 all three sizes (mel and linear bins, one and two sub-transforms per frame, two frames per wave), and the backward
