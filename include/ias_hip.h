@@ -15,10 +15,10 @@ extern "C" {
 #endif
 
 #define IAS_OK 0
-#define IAS_ERR_ARG (-1)
-#define IAS_ERR_UNSUPPORTED (-2)
-#define IAS_ERR_LAUNCH (-3)
-#define IAS_ERR_WORKSPACE (-4)
+#define IAS_ERR_ARG (-1)         /* bad pointer / dimension */
+#define IAS_ERR_UNSUPPORTED (-2) /* shape outside the kernel's limits */
+#define IAS_ERR_LAUNCH (-3)      /* HIP launch failure (hipGetLastError != success) */
+#define IAS_ERR_WORKSPACE (-4)   /* workspace too small */
 
 /* Library version (major*100 + minor). */
 int ias_version(void);

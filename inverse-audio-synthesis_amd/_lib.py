@@ -5,6 +5,7 @@ non-zero status, an exception is raised.
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -19,142 +20,54 @@ _ERRORS = {
     -4: "IAS_ERR_WORKSPACE (workspace too small)",
 }
 
-_c = ctypes
-_P, _I, _LL = _c.c_void_p, _c.c_int, _c.c_longlong
-_F = _c.c_float
+_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
+_VALUE_TYPES = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong,
+                "float": ctypes.c_float, "double": ctypes.c_double}
+_RETURN_TYPES = ("int", "long long")
 
-# name -> (restype, argtypes).  Must list every symbol include/ias_hip.h declares.
-SYMBOLS = {
-    "ias_version": (_I, []),
-    "ias_stream_copy": (_I, [_P, _P, _LL, _P]),
-    "ias_stamp": (_I, [_P, _P]),
-    "ias_voice_workspace_bytes": (_LL, [_I, _I, _I]),
-    "ias_voice_control": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "ias_voice_control_ws": (_I, [_P, _P, _LL, _I, _I, _I, _I, _P]),
-    "ias_voice_render": (_I, [_P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "ias_voice_stage": (_I, [_I, _I, _P, _P, _P, _LL, _I, _I, _I, _I, _P]),
-    "ias_voice_read_status": (_I, [_P, _P, _I, _I, _I, _P]),
-    "ias_voice_read_status_sticky": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ias_voice_peaks_offset": (_LL, [_I, _I, _I]),
-    "ias_voice_ctrl_offset": (_LL, [_I, _I, _I]),
-    "ias_voice_vconst_offset": (_LL, [_I, _I, _I]),
-    "ias_voice_read_peaks": (_I, [_P, _P, _I, _I, _I, _P]),
-    "ias_voice_save_for_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    "ias_voice_backward_form": (_I, [_I, _I]),
-    "ias_voice_grad_tiles": (_I, [_I]),
-    "ias_voice_grad_nscalars": (_I, []),
-    "ias_voice_grad_nplanes": (_I, []),
-    "ias_voice_backward": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ias_voice_norm_scratch_len": (_LL, [_I]),
-    "ias_voice_norm_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
-    "ias_voice_control_backward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    "ias_voice_control_backward_ws_bytes": (_LL, [_I, _I]),
-    "ias_voice_control_backward_ws": (_I, [_I, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P]),
-    "ias_pqmf_out_len": (_I, [_I, _I, _I]),
-    "ias_pqmf_packed_taps_len": (_I, [_I, _I]),
-    "ias_pqmf_pack_taps": (_I, [_P, _P, _I, _I, _P]),
-    "ias_pqmf_modtab_len": (_I, []),
-    "ias_pqmf_build_modtab": (_I, [_P, _I, _I, _P]),
-    "ias_pqmf_analysis": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ias_pqmf_synth_taps_len": (_I, [_I, _I]),
-    "ias_pqmf_pack_synth_taps": (_I, [_P, _P, _I, _I, _P]),
-    "ias_pqmf_synthesis_t": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "ias_stft_num_frames": (_I, [_I, _I, _I]),
-    "ias_stft_partials_count": (_LL, [_I, _I, _I, _I, _I]),
-    "ias_stft_tables_len": (_I, [_I]),
-    "ias_stft_build_tables": (_I, [_I, _P, _P]),
-    "ias_stft_segtab_len": (_LL, [_I, _P, _P, _P, _P, _I]),
-    "ias_stft_build_segtab": (_I, [_I, _P, _P, _P, _P, _I, _P]),
-    "ias_stft_mtables_len": (_LL, [_I, _P, _P, _I]),
-    "ias_stft_build_mtables": (_I, [_I, _P, _P, _P, _P, _P, _I, _P]),
-    "ias_stft": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P]),
-    "ias_stft_loss_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I,
-                                   ctypes.c_float, ctypes.c_float, _P]),
-    "ias_stft_grad_frames": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, ctypes.c_float,
-                                 ctypes.c_float, _P]),
-    "ias_stft_grad_spans": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, ctypes.c_float,
-                                ctypes.c_float, _P, _P]),
-    "ias_stft_grad_span_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
-    "ias_stft_grad_combine": (_I, [_P, _P, _I, _P, _P, _I, _I, _P]),
-    "ias_reduce_partials": (_I, [_P, _LL, _P, _c.c_double, _P, _P]),
-    "ias_mrstft_total": (_I, [_P, _P, _I, _P, _P]),
-    "ias_mrstft_coef": (_I, [_P, _P, _c.c_double, _I, _P, _P]),
-    "ias_l1_partials_count": (_LL, [_LL]),
-    "ias_l1_partials": (_I, [_P, _P, _LL, _P, _P]),
-    "ias_l1_grad": (_I, [_P, _P, _P, _F, _LL, _P, _P]),
-    "ias_l1_rows_partials_count": (_I, [_LL]),
-    "ias_l1_rows": (_I, [_P, _P, _I, _LL, _P, _P, _P]),
-    "ias_stft_loss_backward_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
-    "ias_match_adam_step": (_I, [_P] * 11 + [_I, _I, _F, _F, _F, _F, _P]),
-    "ias_mrstft_rows_partials_count": (_I, [_LL]),
-    "ias_mrstft_rows": (_I, [_P, _P, _I, _LL, _P, _P, _P]),
-    "ias_mrstft_rows_total": (_I, [_P, _P, _I, _I, _P, _P]),
-    "ias_mrstft_coef_rows": (_I, [_P, _P, _c.c_double, _I, _I, _P, _P]),
-    "ias_l1_cdist_workspace_bytes": (_LL, [_I, _I, _LL]),
-    "ias_l1_cdist": (_I, [_P, _P, _I, _I, _LL, _P, _P, _P]),
-    "ias_topk_merge": (_I, [_P, _I, _I, _LL, _LL, _I, _P, _P, _P]),
-    "ias_evolve_sample": (_I, [_P, _P, _P, _I, _I, _I, _I, _LL, _c.c_ulonglong, _LL, _P, _P]),
-    "ias_evolve_update": (_I, [_P, _LL, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _c.c_double, _c.c_double,
-                              _c.c_double, _P]),
-    "ias_pitch_frames": (_LL, [_I, _I, _I, _I]),
-    "ias_pitch_yin": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
-    "ias_onset_flux": (_I, [_P, _I, _I, _I, _I, _F, _P, _P, _P]),
-    "ias_onset_pick": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P]),
-    "ias_segment_gather": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P]),
-    "ias_segment_scatter": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P]),
-    "ias_envelope_num_frames": (_LL, [_I, _I, _I]),
-    "ias_envelope_frames": (_I, [_P, _I, _I, _I, _I, _P, _P]),
-    "ias_envelope_score": (_I, [_P, _P, _I, _I, _I, _c.c_double, _c.c_double, _P, _P]),
-    "ias_resample_plan": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
-    "ias_resample_build_taps": (_I, [_I, _I, _I, _c.c_double, _I, _c.c_double, _P]),
-    "ias_resample_out_len": (_LL, [_LL, _I, _I]),
-    "ias_resample": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "ias_stft_loss_backward_mrstft_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
-    "ias_stft_grad_frames_mrstft_rows": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
-    "ias_stft_grad_spans_mrstft_rows": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P]),
-    "ias_vicreg_workspace_bytes": (_LL, [_I, _I]),
-    "ias_vicreg_loss": (_I, [_P, _P, _P, _P, _LL, _I, _I, _I, _F, _F, _F, _P]),
-    "ias_vicreg_loss_ld": (_I, [_P, _P, _LL, _P, _P, _LL, _I, _I, _I, _F, _F, _F, _P]),
-    "ias_vicreg_backward4_ld": (_I, [_P, _P, _LL, _P, _P, _P, _P, _P, _P, _LL, _P, _LL, _I, _I, _I, _F, _F, _F, _P]),
-    "ias_vicreg_stage": (_I, [_I, _P, _P, _P, _P, _LL, _I, _I, _I, _F, _F, _F, _P]),
-    "ias_conv_out_size": (_I, [_I, _I, _I]),
-    "ias_dwconv_forward": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "ias_dwconv_backward_data": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "ias_dwconv_weight_scratch_hw": (_LL, [_I, _I, _I, _I, _I, _I]),
-    "ias_dwconv_backward_weight": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "ias_pwconv_supported": (_I, [_I, _I]),
-    "ias_pwconv_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ias_pwconv_backward_data": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
-    "ias_pwconv_weight_scratch": (_LL, [_I, _I, _I, _I]),
-    "ias_pwconv_backward_weight": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ias_reduce_partials_multi": (_I, [_P, _I, _P]),
-    "ias_se_plane_reduce": (_I, [_P, _P, _P, _LL, _I, _F, _P]),
-    "ias_se_scale": (_I, [_P, _P, _P, _P, _LL, _I, _F, _P]),
-    "ias_se_mlp_forward": (_I, [_P] * 8 + [_I, _I, _I, _P]),
-    "ias_se_mlp_backward": (_I, [_P] * 13 + [_I, _I, _I, _P]),
-    "ias_conv2x2_patches": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ias_conv2x2_patches_backward": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ias_conv2x2_patches_backward_nchw": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ias_conv2x2_patches_nchw": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "ias_colsum_scratch_floats": (_LL, [_I, _I]),
-    "ias_colsum": (_I, [_P, _P, _P, _I, _I, _P]),
-    "ias_stem_forward": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "ias_stem_weight_scratch": (_LL, [_I]),
-    "ias_stem_backward_weight": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    "ias_bn_scratch_doubles": (_LL, [_I, _I]),
-    "ias_bn_act_forward": (_I, [_P] * 11 + [_I, _I, _I, _F, _F, _I, _P]),
-    "ias_bn_act_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ias_bn1d_groups_forward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P]),
-    "ias_bn1d_groups_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ias_lars_chunk_elems": (_I, []),
-    "ias_lars_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "ias_lars_step_carry": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-}
 
-# Symbols only the diagnostic library exports (include/ias_hip_diag.h).
-DIAG_SYMBOLS = {
-    "ias_vicreg_set_form": (_I, [_I]),
-}
+def parse_prototypes(text):
+    """name -> (restype, argtypes) of every `int | long long ias_*( ... );` declaration in the text of a C header.
+    Comments and preprocessor lines are dropped (an #include is not followed); a pointer of any kind is a c_void_p, a
+    named value one of _VALUE_TYPES, `(void)` no arguments.  Strict: an ias_* declaration of another form, return type
+    or parameter type raises ValueError with the declaration in its message -- a prototype is never guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r'^\s*#.*$|extern\s+"C"\s*\{', " ", text, flags=re.M)
+    table = {}
+    for stmt in text.split(";"):
+        if not re.search(r"\bias_\w*\s*\(", stmt):
+            continue
+        decl = " ".join(stmt.split())
+        m = re.fullmatch(r"([\w ]+?) (ias_\w+) ?\((.*)\)", decl)
+        if not m:
+            raise ValueError(f"cannot parse the declaration `{decl};`")
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+        if ret not in _RETURN_TYPES:
+            raise ValueError(f"return type `{ret}` of `{decl};` is not one of {_RETURN_TYPES}")
+        args = []
+        for param in ([] if params == "void" else params.split(",")):
+            if re.fullmatch(r"[\w ]+\*[\w *]*", param.strip()):
+                args.append(ctypes.c_void_p)
+                continue
+            v = re.fullmatch(r"(?:const )?([a-z ]+) \w+", param.strip())
+            if not v or v.group(1) not in _VALUE_TYPES:
+                raise ValueError(f"parameter `{param.strip()}` of `{decl};` has a type outside {sorted(_VALUE_TYPES)}")
+            args.append(_VALUE_TYPES[v.group(1)])
+        if name in table:
+            raise ValueError(f"{name} is declared twice")
+        table[name] = (_VALUE_TYPES[ret], args)
+    return table
+
+
+def _header_prototypes(header):
+    with open(os.path.join(_INCLUDE, header)) as f:
+        return parse_prototypes(f.read())
+
+
+# name -> (restype, argtypes), read from the declarations the kernel files are compiled against (csrc/ias_common.h
+# includes both headers): the product ABI, and the symbols only the diagnostic library exports.
+SYMBOLS = _header_prototypes("ias_hip.h")
+DIAG_SYMBOLS = _header_prototypes("ias_hip_diag.h")
 DIAG_LIB_PATH = os.path.join(_HERE, "csrc", "libias_hip_diag.so")
 
 _lib = None

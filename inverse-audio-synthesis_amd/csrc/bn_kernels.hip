@@ -586,7 +586,6 @@ static void bn_launch_finapply(hipStream_t stream, const float* x, const float* 
 // 16-byte aligned where x is.
 // pooled (or NULL): also pooled[b][c] = mean_hw y[b][c] ([B,C]), the squeeze-excitation block's average pool, taken by the
 // normalisation's own launch on maps up to 15 x 16.  Not together with res (no layer of the trunk has both).
-extern "C" int ias_se_plane_reduce(const float* x, const float* m, float* out, long long planes, int HW, float scale, void* stream_);   // se_kernels.hip
 extern "C" int ias_bn_act_forward(const float* x, const float* res, const float* weight, const float* bias, float* running_mean,
                                   float* running_var, float* y, float* pooled, float* save_mean, float* save_invstd,
                                   double* scratch, int B, int C, int HW, float eps, float momentum, int act, void* stream_) {

@@ -39,24 +39,19 @@ constexpr bool kIasDiag = false;
 #define ias_diag_env(name) ((const char*)0)
 #endif
 
-// Error codes returned by every C-ABI entry point.
-#define IAS_OK 0
-#define IAS_ERR_ARG (-1)        // bad pointer / dimension
-#define IAS_ERR_UNSUPPORTED (-2)
-#define IAS_ERR_LAUNCH (-3)     // HIP launch failure (hipGetLastError != success)
-#define IAS_ERR_WORKSPACE (-4)  // workspace too small
+// The C ABI: every entry point, the IAS_OK / IAS_ERR_* status codes and struct IasReduceItem are declared once, in the
+// public headers.  Every file that defines an entry point sees them through this include, so a definition whose
+// parameter list differs from its declaration does not compile ("conflicting types"), and a kernel file that calls
+// another file's entry point needs no declaration of its own.  Relative to this file: no compile line needs an -I.
+#include "../../include/ias_hip.h"
+#ifdef IAS_DIAG
+#include "../../include/ias_hip_diag.h"
+#endif
 
 #define IAS_NPARAMS 78
 // torchsynth LFO shape-mix exponent: LFO.__init__'s default `exponent = tensor(e)`, i.e. the fp32 0x402DF854
 #define IAS_LFO_EXPONENT_F 2.7182817459106445f
 #define IAS_NCTRL 5             // mod-matrix outputs: vco1 pitch, vco1 amp, vco2 pitch, vco2 amp, noise amp
-
-// One entry of ias_reduce_partials_multi's table (include/ias_hip.h): out[i] = sum_r partial[r n + i], i < n.
-struct IasReduceItem {
-  const float* partial;
-  float* out;
-  int n, rows;
-};
 
 // Per-voice scalars produced by the control-rate kernel, consumed at audio rate.
 struct IasVoiceConst {

@@ -408,21 +408,9 @@ extern "C" int ias_stft_grad_combine(const float* const* spans_host, const int* 
 //   audio [B,T]; window [n_fft] (device); mel_* : the forward's CSR filterbank (NULL = linear bins, n_out = n_fft/2+1);
 //   target [B,F,n_out] frames-major (what ias_stft wrote for the target); power: 1 (magnitude) or 2 (power);
 //   frame_grad [B,F,n_fft] fp32 scratch; g_audio [B,T] out.  F = ias_stft_num_frames(T, n_fft, hop).
-extern "C" int ias_stft_grad_frames(const float* audio, const float* tables, const int* mel_start, const int* mel_count,
-                                    const int* mel_woff, const float* mel_w, int mel_nnz, int n_out, const float* target,
-                                    const double* coef, float* frame_grad, int B, int T, int n_fft, int hop, int power,
-                                    int loss_mode, float scale, float eps, void* stream);   // csrc/stft_frame_grad_kernels.hip
-extern "C" int ias_stft_grad_spans(const float* audio, const float* tables, const int* mel_start, const int* mel_count,
-                                   const int* mel_woff, const float* mel_w, int mel_nnz, int n_out, const float* target,
-                                   const double* coef, float* chunk_spans, int B, int T, int n_fft, int hop, int power,
-                                   int loss_mode, float scale, float eps, int* plan_host, void* stream);
-extern "C" int ias_stft_grad_frames_mrstft_rows(const float* audio, const float* tables, int n_out, const float* target,
-                                                const double* coef_rows, float* frame_grad, int B, int T, int n_fft,
-                                                int hop, float eps, void* stream);
-extern "C" int ias_stft_grad_spans_mrstft_rows(const float* audio, const float* tables, int n_out, const float* target,
-                                               const double* coef_rows, float* chunk_spans, int B, int T, int n_fft,
-                                               int hop, float eps, int* plan_host, void* stream);
-
+// (The frame part called below -- ias_stft_grad_frames, ias_stft_grad_spans and their _mrstft_rows forms -- is defined
+// in stft_frame_grad_kernels.hip and declared, like every entry point, in include/ias_hip.h.)
+//
 // ROWS: g_loss is [B] (one cotangent per row, loss_mode 1).  CROW: coef is [B][2] (one pair per row, loss_mode 2,
 // g_loss NULL).
 template <bool ROWS, bool CROW>

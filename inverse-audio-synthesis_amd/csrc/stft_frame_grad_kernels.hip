@@ -19,7 +19,6 @@
 //             y[2m] + i y[2m+1] = IDFT(Zin)[m],  Zin[k] = (a[k] + conj a[N/2-k]) / 2 + i (b[k] + conj b[N/2-k]) / 2;
 //             the inverse transform is the same three passes on conj(Zin), conjugated again at the end
 //   output    frame_grad[f][n] = window[n] y[n]  (the overlap-add stays in stft_grad_ola_kernel)
-extern "C" int ias_stft_num_frames(int T, int n_fft, int hop);
 struct SgwArgs {
   const float* audio; const float* tables; const float* target; const double* coef; float* frame_grad;
   const int* mel_start; const int* mel_count; const int* mel_woff; const float* mel_w;   // MEL: the forward's CSR filters

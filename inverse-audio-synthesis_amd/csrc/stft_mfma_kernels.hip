@@ -35,8 +35,6 @@
 #include <vector>
 #include <algorithm>
 
-extern "C" int ias_stft_num_frames(int T, int n_fft, int hop);
-
 // ------------------------------------------------------------------------------------------------ host: constant block
 static bool sm_supported(int n_fft) { return n_fft == 512 || n_fft == 1024 || n_fft == 2048; }
 

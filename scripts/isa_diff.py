@@ -32,6 +32,11 @@ def makefile_flags(csrc):
     arch = re.search(r"^ARCH\s*\?=\s*(\S+)", text, re.M).group(1)
     base = re.search(r"^HIPFLAGS\s*=\s*(.*)$", text, re.M).group(1).replace("$(ARCH)", arch).split()
     extra = {}
+    # one list of files and their flag as a target-specific variable: `$(LIST:%=%.o) ...: FILEFLAGS = <flags>`
+    for var, flags in re.findall(r"^\$\((\w+):%=%\.o\).*:\s*\w+\s*\+?=\s*(.*)$", text, re.M):
+        for stem in re.search(rf"^{var}\s*=\s*(.*)$", text, re.M).group(1).split():
+            extra[stem + ".hip"] = flags.split()
+    # trees before that: a rule of its own per such file
     for stem, recipe in re.findall(r"^(\w+)\.o:.*\n\t(.*)$", text, re.M):
         words = recipe.split()
         extra[stem + ".hip"] = [w for w in words if w.startswith("-f") and w not in base]

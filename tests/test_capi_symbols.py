@@ -24,6 +24,87 @@ def test_header_symbols_exported(lib):
         assert n in names, f"{n} bound in _lib.py but not declared in include/ias_hip.h"
 
 
+_P, _I, _LL, _ULL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_ulonglong
+_F, _D = ctypes.c_float, ctypes.c_double
+# Written out by hand from the C declarations: between them every type _lib.parse_prototypes maps.
+PINNED = {
+    "ias_stft": (_I, [_P] * 8 + [_I] + [_P] * 5 + [_I] * 7 + [_F, _P]),      # 23 arguments, a float among ints
+    "ias_evolve_sample": (_I, [_P, _P, _P, _I, _I, _I, _I, _LL, _ULL, _LL, _P, _P]),
+    "ias_reduce_partials": (_I, [_P, _LL, _P, _D, _P, _P]),
+    "ias_voice_workspace_bytes": (_LL, [_I, _I, _I]),
+    "ias_reduce_partials_multi": (_I, [_P, _I, _P]),                        # const IasReduceItem*
+    "ias_version": (_I, []),                                                # (void)
+}
+PINNED_DIAG = {"ias_vicreg_set_form": (_I, [_I])}
+
+
+def test_prototypes_derived_from_the_headers_match_pinned_ones():
+    from inverse_audio_synthesis_amd import _lib
+    for table, pinned in ((_lib.SYMBOLS, PINNED), (_lib.DIAG_SYMBOLS, PINNED_DIAG)):
+        for name, (res, args) in pinned.items():
+            got_res, got_args = table[name]
+            assert got_res is res, name
+            assert len(got_args) == len(args), name
+            for i, (g, a) in enumerate(zip(got_args, args)):
+                assert g is a, f"{name}: argument {i} is bound as {g.__name__}, the declaration says {a.__name__}"
+    assert len(PINNED["ias_stft"][1]) == 23
+    assert len(_lib.SYMBOLS) == 120 and not set(_lib.SYMBOLS) & set(_lib.DIAG_SYMBOLS)   # the diag header's #include is not followed
+
+
+def test_prototype_parser_is_strict():
+    import pytest
+    from inverse_audio_synthesis_amd._lib import parse_prototypes
+    ok = "/* int ias_no(short a); */ int ias_a(const float* const* x, unsigned long long seed, double d, void* stream); // int ias_b(\n"
+    assert parse_prototypes(ok) == {"ias_a": (_I, [_P, _ULL, _D, _P])}
+    for bad in ("int ias_a(int n, short s);",                  # parameter type outside the mapping
+                "int ias_a(unsigned n);",
+                "int ias_a(long n);",
+                "int ias_a(int);",                             # unnamed: `long long` could not be told from `long n`
+                "int ias_a();",
+                "float ias_a(int n);",                         # return type outside the mapping
+                "unsigned long long ias_a(int n);",
+                "const char* ias_a(int n);",
+                "int ias_a(int (*cb)(int), int n);",           # forms it cannot fully match
+                "int ias_a(int n) __attribute__((pure));",
+                "static inline int ias_a(int n) { return n; }",
+                "int ias_a(int n[4]);",
+                "int ias_a(int n); int ias_a(int n);"):
+        with pytest.raises(ValueError, match="ias_a"):
+            parse_prototypes(bad)
+
+
+_CSRC = os.path.join(ROOT, "inverse-audio-synthesis_amd", "csrc")
+
+
+def _code(path):
+    text = open(path).read()
+    return re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+
+
+def _reaches(path, target, seen):
+    """does `path` include `target`, directly or through its quoted includes (resolved relative to the including file)?"""
+    for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', _code(path), re.M):
+        p = os.path.normpath(os.path.join(os.path.dirname(path), inc))
+        if p == target or (p not in seen and os.path.exists(p) and not seen.add(p) and _reaches(p, target, seen)):
+            return True
+    return False
+
+
+def test_every_file_that_defines_an_entry_point_is_compiled_against_its_declaration():
+    """With C linkage nothing but the compiler compares a definition with include/ias_hip.h, and only where it sees both:
+    every .hip file with an extern "C" definition includes the header (through csrc/ias_common.h), and none declares an
+    ias_* entry point by hand."""
+    header = os.path.join(ROOT, "include", "ias_hip.h")
+    files = sorted(f for f in os.listdir(_CSRC) if f.endswith(".hip"))
+    defining = [f for f in files if re.search(r'extern\s+"C"[^;{]*\{', _code(os.path.join(_CSRC, f)))]
+    assert len(defining) >= 23
+    for f in defining:
+        assert _reaches(os.path.join(_CSRC, f), header, set()), f"{f} defines extern \"C\" functions without include/ias_hip.h"
+    for f in files:
+        decl = re.findall(r'extern\s+"C"[^;{]*\bias_\w+\s*\([^;{]*;', _code(os.path.join(_CSRC, f)))
+        assert not decl, f"{f} re-declares {decl}"
+
+
 def test_version_and_arg_checks(lib):
     assert lib.ias_version() >= 100
     # pure host-side argument validation (no GPU touched)
