@@ -1,4 +1,4 @@
-"""VICReg model + loss -- drop-in for /root/reference/vicreg.py on MI355X.
+"""VICReg model + loss -- drop-in for the reference's vicreg.py on MI355X.
 
 Same public names and contracts: ``VICReg(cfg, backbone_audio, backbone_param)`` with
 ``.forward(audio, params) -> (x, y)`` and ``.loss(x, y) -> (loss, repr_loss, std_loss, cov_loss)``
@@ -6,8 +6,10 @@ Same public names and contracts: ``VICReg(cfg, backbone_audio, backbone_param)``
 ``FullGatherLayer`` (:79-95, which in the reference raises NameError because ``dist`` is never
 imported -- here it works, over RCCL), ``exclude_bias_and_norm`` (:98-99).
 
-The loss forward is the HIP path (csrc/vicreg_kernels.hip: fp32 column statistics, bf16 MFMA Gram with
-fp32 accumulation, fused off-diagonal square-sum).  The backward is HIP as well (ias_vicreg_backward4_ld): closed form
+The loss forward is the HIP path (csrc/vicreg_kernels.hip: fp32 column statistics, final reduction and the C ABI; the
+covariance term as a bf16 MFMA Gram with fp32 accumulation and fused square-sum, B x B in csrc/vicreg_grad_kernels.hip
+where the padded batch is no larger than the embedding, else D x D in csrc/vicreg_dxd_kernels.hip).  The backward is HIP
+as well (ias_vicreg_backward4_ld, csrc/vicreg_grad_kernels.hip): closed form
 with the B x B Gram identity  d cov_loss / d xc = 4/((Bc-1)^2 D) * ((xc xc^T) xc - xc diag(xc^T xc)) -- both
 products on the matrix cores, one elementwise epilogue -- so no D x D matrix is ever materialised in either direction.
 """
@@ -26,23 +28,37 @@ def _cotangent_ptrs(grads):
     return [None if k is None else k.data_ptr() for k in keep], keep
 
 
+def _launch_forward(x_ptr, y_ptr, ld, B, D, consts, device):
+    """The loss of x, y [B, D] fp32 at two device pointers with row stride ld floats; consts = (cfg_batch, sim, std, cov).
+    -> (out[4] = loss, repr, std, cov; the workspace, which keeps the column statistics / centred bf16 copies the backward
+    needs)."""
+    lib = _lib.load()
+    need = lib.ias_vicreg_workspace_bytes(B, D)
+    _lib.check(min(int(need), 0), "ias_vicreg_workspace_bytes")
+    ws = torch.empty(int(need), dtype=torch.uint8, device=device)
+    out = torch.empty(4, dtype=torch.float32, device=device)
+    _lib.check(lib.ias_vicreg_loss_ld(x_ptr, y_ptr, ld, _lib.ptr(out), _lib.ptr(ws), ws.numel(), B, D, *consts, _lib.stream()),
+               "ias_vicreg_loss_ld")
+    return out, ws
+
+
+def _launch_backward(x_ptr, y_ptr, ld, grads, gx_ptr, gy_ptr, ldg, ws, B, D, consts):
+    """gx, gy [B, D] (row stride ldg) <- the cotangents `grads` of the four outputs, on the workspace of the forward."""
+    cot, keep = _cotangent_ptrs(grads)     # (`keep` lives until the launch has been issued)
+    _lib.check(_lib.load().ias_vicreg_backward4_ld(x_ptr, y_ptr, ld, *cot, gx_ptr, gy_ptr, ldg, _lib.ptr(ws), ws.numel(), B, D,
+                                                   *consts, _lib.stream()), "ias_vicreg_backward4_ld")
+
+
 class _VICRegLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y, cfg_batch, sim_coeff, std_coeff, cov_coeff):
-        lib = _lib.load()
         xc, yc = x.detach().contiguous(), y.detach().contiguous()
         _lib.require_f32(xc, yc)
         assert xc.shape == yc.shape and xc.dim() == 2
         B, D = xc.shape
-        need = lib.ias_vicreg_workspace_bytes(B, D)
-        _lib.check(min(int(need), 0), "ias_vicreg_workspace_bytes")
-        ws = torch.empty(int(need), dtype=torch.uint8, device=xc.device)
-        out = torch.empty(4, dtype=torch.float32, device=xc.device)
-        st = lib.ias_vicreg_loss(_lib.ptr(xc), _lib.ptr(yc), _lib.ptr(out), _lib.ptr(ws), ws.numel(), B, D,
-                                 int(cfg_batch), float(sim_coeff), float(std_coeff), float(cov_coeff), _lib.stream())
-        _lib.check(st, "ias_vicreg_loss")
-        ctx.save_for_backward(xc, yc, ws)     # the workspace keeps the column statistics / centred bf16 copies
         ctx.consts = (int(cfg_batch), float(sim_coeff), float(std_coeff), float(cov_coeff))
+        out, ws = _launch_forward(_lib.ptr(xc), _lib.ptr(yc), D, B, D, ctx.consts, xc.device)
+        ctx.save_for_backward(xc, yc, ws)
         # unused outputs (repr / std / cov when only the loss is differentiated) arrive as None in backward instead of as
         # three freshly filled zero tensors
         ctx.set_materialize_grads(False)
@@ -51,13 +67,10 @@ class _VICRegLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, g_repr, g_std, g_cov):
         x, y, ws = ctx.saved_tensors
-        cfg_batch, sim, std, cov = ctx.consts
         B, D = x.shape
-        lib = _lib.load()
         grads = (g_loss, g_repr, g_std, g_cov)
         if all(g is None for g in grads):
             return None, None, None, None, None, None
-        cot = _cotangent_ptrs(grads)
         if D % 8 != 0:
             # The backward kernels move 16-byte groups of 8 bf16 columns.  An embedding width that is not a multiple of 8 (none
             # of the reference's configurations; toy shapes) runs them on the inputs padded with zero COLUMNS: a zero column
@@ -67,22 +80,13 @@ class _VICRegLossFn(torch.autograd.Function):
             xp, yp = x.new_zeros((B, D8)), y.new_zeros((B, D8))
             xp[:, :D].copy_(x)
             yp[:, :D].copy_(y)
-            need = lib.ias_vicreg_workspace_bytes(B, D8)
-            _lib.check(min(int(need), 0), "ias_vicreg_workspace_bytes")
-            wsp = torch.empty(int(need), dtype=torch.uint8, device=x.device)
-            outp = torch.empty(4, dtype=torch.float32, device=x.device)
-            _lib.check(lib.ias_vicreg_loss(_lib.ptr(xp), _lib.ptr(yp), _lib.ptr(outp), _lib.ptr(wsp), wsp.numel(), B, D8, cfg_batch,
-                                           sim, std, cov, _lib.stream()), "ias_vicreg_loss")
+            _, wsp = _launch_forward(_lib.ptr(xp), _lib.ptr(yp), D8, B, D8, ctx.consts, x.device)
             gxp, gyp = torch.empty_like(xp), torch.empty_like(yp)
-            _lib.check(lib.ias_vicreg_backward4_ld(_lib.ptr(xp), _lib.ptr(yp), D8, *cot[0], _lib.ptr(gxp), _lib.ptr(gyp), D8,
-                                                   _lib.ptr(wsp), wsp.numel(), B, D8, cfg_batch, sim, std, cov, _lib.stream()),
-                       "ias_vicreg_backward4_ld")
+            _launch_backward(_lib.ptr(xp), _lib.ptr(yp), D8, grads, _lib.ptr(gxp), _lib.ptr(gyp), D8, wsp, B, D8, ctx.consts)
             k = float(D8) / float(D)
             return gxp[:, :D] * k, gyp[:, :D] * k, None, None, None, None
         gx, gy = torch.empty_like(x), torch.empty_like(y)
-        st = lib.ias_vicreg_backward4_ld(_lib.ptr(x), _lib.ptr(y), D, *cot[0], _lib.ptr(gx), _lib.ptr(gy), D, _lib.ptr(ws),
-                                         ws.numel(), B, D, cfg_batch, sim, std, cov, _lib.stream())
-        _lib.check(st, "ias_vicreg_backward4_ld")
+        _launch_backward(_lib.ptr(x), _lib.ptr(y), D, grads, _lib.ptr(gx), _lib.ptr(gy), D, ws, B, D, ctx.consts)
         return gx, gy, None, None, None, None
 
 
@@ -93,39 +97,28 @@ class _VICRegPairLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xy, cfg_batch, sim_coeff, std_coeff, cov_coeff):
-        lib = _lib.load()
         xyc = xy.detach().contiguous()
         _lib.require_f32(xyc)
         assert xyc.dim() == 2 and xyc.shape[1] % 2 == 0
         B, D = xyc.shape[0], xyc.shape[1] // 2
         assert D % 8 == 0, "pair form: embedding width must be a multiple of 8 (use vicreg_loss on the two halves)"
-        need = lib.ias_vicreg_workspace_bytes(B, D)
-        _lib.check(min(int(need), 0), "ias_vicreg_workspace_bytes")
-        ws = torch.empty(int(need), dtype=torch.uint8, device=xyc.device)
-        out = torch.empty(4, dtype=torch.float32, device=xyc.device)
-        base = xyc.data_ptr()
-        st = lib.ias_vicreg_loss_ld(base, base + 4 * D, 2 * D, _lib.ptr(out), _lib.ptr(ws), ws.numel(), B, D,
-                                    int(cfg_batch), float(sim_coeff), float(std_coeff), float(cov_coeff), _lib.stream())
-        _lib.check(st, "ias_vicreg_loss_ld")
-        ctx.save_for_backward(xyc, ws)
         ctx.consts = (int(cfg_batch), float(sim_coeff), float(std_coeff), float(cov_coeff))
+        base = xyc.data_ptr()
+        out, ws = _launch_forward(base, base + 4 * D, 2 * D, B, D, ctx.consts, xyc.device)
+        ctx.save_for_backward(xyc, ws)
         ctx.set_materialize_grads(False)
         return out[0], out[1], out[2], out[3]
 
     @staticmethod
     def backward(ctx, g_loss, g_repr, g_std, g_cov):
         xy, ws = ctx.saved_tensors
-        cfg_batch, sim, std, cov = ctx.consts
         B, D = xy.shape[0], xy.shape[1] // 2
         grads = (g_loss, g_repr, g_std, g_cov)
         if all(g is None for g in grads):
             return None, None, None, None, None
         g = torch.empty_like(xy)
         base, gbase = xy.data_ptr(), g.data_ptr()
-        cot = _cotangent_ptrs(grads)
-        st = _lib.load().ias_vicreg_backward4_ld(base, base + 4 * D, 2 * D, *cot[0], gbase, gbase + 4 * D, 2 * D,
-                                                 _lib.ptr(ws), ws.numel(), B, D, cfg_batch, sim, std, cov, _lib.stream())
-        _lib.check(st, "ias_vicreg_backward4_ld")
+        _launch_backward(base, base + 4 * D, 2 * D, grads, gbase, gbase + 4 * D, 2 * D, ws, B, D, ctx.consts)
         return g, None, None, None, None
 
 

@@ -37,7 +37,8 @@ def test_loss_golden(lib, dev, golden_dir, tag):
     _check(out, g[tag + "_out"])
 
 
-@pytest.mark.parametrize("B,D", [(2, 1), (3, 64), (17, 130), (64, 127), (200, 1000)])
+# (129, 130): batch > 128 with D < 256 -- the 128-tile feature-side kernel (vicreg_gram_kernel), two tile rows, ragged last tile
+@pytest.mark.parametrize("B,D", [(2, 1), (3, 64), (17, 130), (64, 127), (200, 1000), (129, 130)])
 def test_loss_ragged_shapes(lib, dev, B, D):
     from inverse_audio_synthesis_amd.vicreg import vicreg_loss
     x, y = randn((B, D), 1) * 1.3 + 0.2, randn((B, D), 2) * 0.5
@@ -54,7 +55,7 @@ GRAD_RTOL = 2e-3   # of the largest gradient element (bf16 operands, fp32 accumu
 
 # (widths that are not a multiple of 8 -- 130, 127, 12, 3: the HIP kernels on zero-padded columns, vicreg._VICRegLossFn.backward)
 @pytest.mark.parametrize("B,D,cfgB", [(32, 256, 48), (128, 1024, 128), (200, 512, 200), (17, 136, 17), (17, 130, 17),
-                                      (64, 127, 64), (8, 12, 8), (5, 3, 5)])
+                                      (64, 127, 64), (8, 12, 8), (5, 3, 5), (129, 130, 129)])
 def test_backward_matches_autograd_of_oracle(lib, dev, B, D, cfgB):
     from inverse_audio_synthesis_amd.vicreg import vicreg_loss
     x0, y0 = randn((B, D), 5) * 0.8, randn((B, D), 6) * 1.1 + 0.3   # std < 1 and > 1 columns both occur
