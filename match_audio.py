@@ -5,7 +5,8 @@
                           [--bank-batches NB] [--bank-stream CHUNK] [--evolve G] [--evolve-population M]
                           [--evolve-elites K] [--evolve-sigma S0] [--pitch] [--pitch-lo MIDI] [--pitch-hi MIDI]
                           [--envelope] [--envelope-generations G] [--envelope-population M]
-                          [--split] [--onset-delta D] [--max-notes K] [--fade-ms MS] [--loss LOSS] [key=value ...]
+                          [--split] [--onset-delta D] [--max-notes K] [--fade-ms MS] [--loss LOSS] [--report]
+                          [key=value ...]
 
 ``key=value`` are config overrides as for pretrain.py / audio_to_params.py (``torchsynth.rate``,
 ``torchsynth.buffer_size_seconds``, ``mel.*``); the matcher's own settings are flags.  Input WAVs are 16-, 24- or 32-bit
@@ -43,7 +44,11 @@ with a warning when there are more) and ``onset.split_notes`` cuts one synth buf
 see the notes exactly as they see files.  Per input NAME the script writes NAME.notes.json ({input, rate, notes}: per
 note ``onset_sample``, ``onset_seconds``, ``length_samples``, ``strength``, ``gain`` and the fields of a params.json record)
 and NAME.match.wav at the file's full length: the best renders, each scaled by ``gain`` (the RMS of the target note over
-the RMS of its render) and put back at its onset (``onset.join_notes``)."""
+the RMS of its render) and put back at its onset (``onset.join_notes``).
+``--report`` (off by default) compares every best render with its target once after the fit, in figures that do not depend
+on ``--loss``: ``report.Reporter`` (the ``mel.*`` settings for its mel plan) gives ``lsd_db``, ``spectral_convergence``,
+``logmel_l1_db``, ``mcd_db``, the counted ``frames`` and ``mel_frames``, ``envelope_db``, ``f0_cents`` (null where either side
+is unvoiced) and ``voiced``.  Each record (each note under ``--split``) and each stdout line gains ``report``."""
 import argparse
 import json
 import os
@@ -253,6 +258,9 @@ def parse_args(argv=None):
     ap.add_argument("--max-notes", type=int, default=256, metavar="K", help="--split: notes kept per file")
     ap.add_argument("--fade-ms", type=float, default=5.0, metavar="MS",
                     help="--split: linear fade-out of a note that is cut by the next onset or by the synth buffer")
+    ap.add_argument("--report", action="store_true",
+                    help="compare each best render with its target in loss-independent figures (report.Reporter) and "
+                         "write them into every record and stdout line as `report`")
     args = ap.parse_args(argv)
     files = [a for a in args.inputs if "=" not in a]
     overrides = [a for a in args.inputs if "=" in a]
@@ -385,8 +393,17 @@ def evolve_stage(args, stage, target, init, prov):
     return found.params01[:, :nS].contiguous() if nS > 1 else found.params01[:, 0].contiguous()
 
 
-def record(args, res, prov, i, name):
-    """The fields of sound i's params.json record."""
+def report_stage(cfg, rate, audio, target):
+    """--report: the best renders against their targets -> one dict of ``report.MatchReport``'s fields per sound."""
+    from inverse_audio_synthesis_amd.report import Reporter
+    try:
+        return Reporter(rate, mel_kwargs=dict(cfg.mel))(audio, target).as_records()
+    except ValueError as e:
+        sys.exit(f"match_audio.py: --report: {e}")
+
+
+def record(args, res, prov, i, name, reports=None):
+    """The fields of sound i's params.json record; with --report, ``reports[i]`` as ``report``."""
     rec = {"input": name, "loss_kind": args.loss, "steps": args.steps,
            "initial_loss": float(res.initial_loss[i]), "final_loss": float(res.loss[i]),
            "skipped": int(res.skipped[i]), "init": args.init, "params": params_record(res.params01[i])}
@@ -408,19 +425,22 @@ def record(args, res, prov, i, name):
         rec["envelope"] = {"sounding": bool(fit.sounding[i]), "distance": float(fit.dist[i]),
                            "start_distance": float(fit.start_dist[i]),
                            **{name: float(v) for name, v in zip(COLUMNS, fit.units[i])}}
+    if reports is not None:
+        rec["report"] = reports[i]
     return rec
 
 
-def file_docs(args, files, rate, tg, res, prov):
+def file_docs(args, files, rate, tg, res, prov, reports=None):
     """-> (the best renders [files, T], NAME.params.json's content per file, its stdout line per file)."""
-    docs = [record(args, res, prov, i, os.path.basename(f)) for i, f in enumerate(files)]
+    docs = [record(args, res, prov, i, os.path.basename(f), reports) for i, f in enumerate(files)]
     if args.resample:
         for doc, sr in zip(docs, tg.in_rates):
             doc["input_rate"], doc["synth_rate"] = int(sr), rate
-    return res.audio, docs, [{key: doc[key] for key in ("input", "initial_loss", "final_loss")} for doc in docs]
+    keys = ("input", "initial_loss", "final_loss") + (("report",) if reports is not None else ())
+    return res.audio, docs, [{key: doc[key] for key in keys} for doc in docs]
 
 
-def notes_docs(args, files, rate, tg, res, prov):
+def notes_docs(args, files, rate, tg, res, prov, reports=None):
     """--split -> (the recordings [files, L] put together from the best renders, NAME.notes.json's content per file, its
     stdout line per file)."""
     from inverse_audio_synthesis_amd.onset import join_notes, note_gains
@@ -435,13 +455,16 @@ def notes_docs(args, files, rate, tg, res, prov):
         for s in [s for s, r in enumerate(rows) if r == i]:
             note = {"onset_sample": starts[s], "onset_seconds": starts[s] / rate, "length_samples": lengths[s],
                     "strength": strengths[s], "gain": gains[s]}
-            note.update(record(args, res, prov, s, os.path.basename(f)))
+            note.update(record(args, res, prov, s, os.path.basename(f), reports))
             notes.append(note)
         docs.append({"input": os.path.basename(f), "rate": rate, "notes": notes})
         if args.resample:
             docs[i]["input_rate"] = int(tg.in_rates[i])
     lines = [{"input": doc["input"], "notes": len(doc["notes"]), "final_loss": [n["final_loss"] for n in doc["notes"]]}
              for doc in docs]
+    if reports is not None:
+        for line, doc in zip(lines, docs):
+            line["report"] = [n["report"] for n in doc["notes"]]
     return joined, docs, lines
 
 
@@ -493,7 +516,8 @@ def main(argv=None):
     res = matcher.fit(tg.audio, init_params01=init, steps=args.steps, return_audio=True)
     os.makedirs(args.out, exist_ok=True)
     make_docs = notes_docs if args.split else file_docs
-    audio, docs, lines = make_docs(args, files, rate, tg, res, prov)
+    reports = report_stage(cfg, rate, res.audio, tg.audio) if args.report else None
+    audio, docs, lines = make_docs(args, files, rate, tg, res, prov, reports)
     write_outputs(args, files, rate, tg, audio, docs, lines)
 
 
