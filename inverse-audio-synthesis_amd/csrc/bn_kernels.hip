@@ -705,20 +705,24 @@ __global__ __launch_bounds__(BN1_THREADS) void bn1d_groups_forward_kernel(
   const float inv_n = 1.0f / (float)n, unbias = (float)n / (float)(n - 1);
   for (int g0 = 0; g0 < G; g0 += GB) {                   // (G % GB == 0: the launcher)
     float xv[GB][RPT > 0 ? RPT : 1];
-    float s[GB], q[GB];
+    float s[GB], q[GB], k[GB];
 #pragma unroll
     for (int j = 0; j < GB; ++j) {
       const float* zg = z + (size_t)(g0 + j) * n * F + fc;
+      // the sum is taken of x - K, K = the group's first row (as the 2-D kernels shift by x[0, c, 0]): a column whose mean
+      // is large against its spread loses nothing to the size of the mean, and a constant column has mean K and
+      // variance 0 exactly (unshifted, its rounded mean left a residue that invstd = 1 / sqrt(eps) multiplied by 316)
+      k[j] = zg[0] + lb;
       s[j] = 0.0f;
       if (RPT > 0) {
 #pragma unroll
         for (int i = 0; i < RPT; ++i) {
           const int r = ty + i * BN1_RG;
-          xv[j][i] = r < n ? zg[(size_t)r * F] + lb : 0.0f;
-          s[j] += xv[j][i];
+          xv[j][i] = r < n ? zg[(size_t)r * F] + lb : k[j];     // (rows past the group add K - K = 0)
+          s[j] += xv[j][i] - k[j];
         }
       } else {
-        for (int r = ty; r < n; r += BN1_RG) s[j] += zg[(size_t)r * F] + lb;
+        for (int r = ty; r < n; r += BN1_RG) s[j] += (zg[(size_t)r * F] + lb) - k[j];
       }
     }
     bn1_reduce<GB>(s, red, tx, ty);
@@ -726,7 +730,7 @@ __global__ __launch_bounds__(BN1_THREADS) void bn1d_groups_forward_kernel(
 #pragma unroll
     for (int j = 0; j < GB; ++j) {
       const float* zg = z + (size_t)(g0 + j) * n * F + fc;
-      mean[j] = s[j] * inv_n;
+      mean[j] = k[j] + s[j] * inv_n;
       q[j] = 0.0f;
       if (RPT > 0) {
 #pragma unroll

@@ -35,3 +35,29 @@ def vicreg_backward_closed_form(x, y, gcoef, cfg_batch, sim, std, cov):
         return b * d_std + c * d_cov
 
     return a * d_repr + branch(x), -a * d_repr + branch(y)
+
+
+SENT, GUARD = -777.0, 64
+
+
+class Guarded:
+    """A device tensor `t` of `shape` inside a 1-D buffer with GUARD sentinels on each side (and sentinels in it until it is
+    written): what a kernel stores outside its output, or does not store at all, stays visible."""
+
+    def __init__(self, dev, shape, init=None, dtype=torch.float32):
+        n = 1
+        for d in shape:
+            n *= d
+        self.buf = torch.full((n + 2 * GUARD,), SENT, dtype=dtype, device=dev)
+        self.t = self.buf[GUARD:GUARD + n].view(shape)
+        if init is not None:
+            self.t.copy_(init)
+
+    def guards_intact(self):
+        return bool((self.buf[:GUARD] == SENT).all()) and bool((self.buf[self.buf.numel() - GUARD:] == SENT).all())
+
+    def untouched(self):
+        return bool((self.buf == SENT).all())
+
+    def cpu(self):
+        return self.t.detach().cpu().clone()
