@@ -635,7 +635,11 @@ int ias_vicreg_stage(int stage, const float* x, const float* y, float* out, void
 
 /* ---- AudioEmbedding trunk: the depthwise convolutions and the stem of torchvision's mobilenet_v3_small.features
  * (reference vicreg_audio_params.py:52-54, audioembed.py:61), NCHW fp32, padding (K-1)/2, no bias.
- * K in {3, 5}, stride S in {1, 2}.  ias_conv_out_size: output extent of one spatial dimension. */
+ * K in {3, 5}, stride S in {1, 2}.  ias_conv_out_size: output extent of one spatial dimension.
+ * Width limit: planes too wide for a wave are staged in LDS as tiles of at least K padded rows (the weight gradient: and
+ * 256 K K floats of partial sums).  ias_dwconv_forward, _backward_data and _backward_weight return IAS_ERR_UNSUPPORTED,
+ * before any launch, where that tile needs more than 65 536 bytes of dynamic LDS: rows of about 2000 floats and more for
+ * the K = 5 weight gradient (4690 at K = 3), about 3270 (K = 5) / 5460 (K = 3) for the forward and the input gradient. */
 int ias_conv_out_size(int n, int K, int S);
 int ias_dwconv_forward(const float* x, const float* w, float* out, int B, int C, int H, int W, int K, int S, void* stream);
 int ias_dwconv_backward_data(const float* g, const float* w, float* gx, int B, int C, int H, int W, int K, int S,

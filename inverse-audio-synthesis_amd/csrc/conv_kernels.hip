@@ -521,6 +521,10 @@ __global__ __launch_bounds__(CV_THREADS) void dw_tile_bwd_s2_kernel(const float*
 
 struct DwTile { int pp, rows_out, Wp, ntiles; size_t lds; unsigned mWp, mRows; };
 #define DW_MAX_TILES 8
+// Dynamic LDS a launch may ask for without hipFuncSetAttribute (none is set in this file).  A tile holds at least K padded
+// rows, the weight gradient 256 K K floats of partial sums besides: rows wider than ~2000 floats (K = 5, weight gradient)
+// or ~3270 (forward, input gradient) do not fit, and the entries refuse them before the launch.
+#define DW_MAX_LDS 65536
 // floor(n / d) = umulhi(n, dw_magic(d)) for n < 2^20, d < 2^11 (the staged tile's index space)
 static unsigned dw_magic(int d) { return d <= 1 ? 0u /* callers never divide by 1 this way */ : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 static DwTile dw_tile_geometry(int H, int W, int Ho, int Wo, int K, int S, int mode) {
@@ -1063,6 +1067,7 @@ extern "C" int ias_dwconv_forward(const float* x, const float* w, float* out, in
     return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
   }
   const DwTile t = dw_tile_geometry(H, W, Ho, Wo, K, S, 0);
+  if (t.lds > DW_MAX_LDS) return IAS_ERR_UNSUPPORTED;
   DW_TILE_DISPATCH(0, dim3((planes + t.pp - 1) / t.pp, t.ntiles), dim3(CV_THREADS), t.lds, (hipStream_t)stream_, x, w,
                    (const float*)nullptr, out, C, H, W, Ho, Wo, planes, t.pp, t.rows_out, t.Wp, 0, t.mWp, t.mRows);
   return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
@@ -1084,6 +1089,7 @@ extern "C" int ias_dwconv_backward_data(const float* g, const float* w, float* g
       return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
     }
     const DwTile t = dw_tile_geometry(Ho, Wo, H, W, K, 1, 0);
+    if (t.lds > DW_MAX_LDS) return IAS_ERR_UNSUPPORTED;
     DW_TILE_DISPATCH(0, dim3((planes + t.pp - 1) / t.pp, t.ntiles), dim3(CV_THREADS), t.lds, (hipStream_t)stream_, g, w,
                      (const float*)nullptr, gx, C, Ho, Wo, H, W, planes, t.pp, t.rows_out, t.Wp, 1, t.mWp, t.mRows);
   } else if ((size_t)(Ho + 2) * (Wo + 2) <= 12288 && !ias_diag_env("IAS_DW_S2_DIRECT")) {
@@ -1136,6 +1142,7 @@ extern "C" int ias_dwconv_backward_weight(const float* x, const float* g, float*
     return hipGetLastError() == hipSuccess ? nchunk : IAS_ERR_LAUNCH;
   }
   const DwTile t = dw_tile_geometry(H, W, Ho, Wo, K, S, 1);
+  if (t.lds > DW_MAX_LDS) return IAS_ERR_UNSUPPORTED;
   DW_TILE_DISPATCH(1, dim3((planes + t.pp - 1) / t.pp, t.ntiles), dim3(CV_THREADS), t.lds, (hipStream_t)stream_, x,
                    (const float*)nullptr, g, scratch, C, H, W, Ho, Wo, planes, t.pp, t.rows_out, t.Wp, 0, t.mWp, t.mRows);
   const int n = C * K * K;   // scratch is [tile][b][c][K K]: the partials of a channel are n floats apart

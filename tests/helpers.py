@@ -42,22 +42,28 @@ SENT, GUARD = -777.0, 64
 
 class Guarded:
     """A device tensor `t` of `shape` inside a 1-D buffer with GUARD sentinels on each side (and sentinels in it until it is
-    written): what a kernel stores outside its output, or does not store at all, stays visible."""
+    written): what a kernel stores outside its output, or does not store at all, stays visible.  `sent`: the sentinel
+    (NaN for a kernel's INPUTS: a read outside the payload that enters arithmetic poisons the result)."""
 
-    def __init__(self, dev, shape, init=None, dtype=torch.float32):
+    def __init__(self, dev, shape, init=None, dtype=torch.float32, sent=SENT):
         n = 1
         for d in shape:
             n *= d
-        self.buf = torch.full((n + 2 * GUARD,), SENT, dtype=dtype, device=dev)
+        self.sent = sent
+        self.buf = torch.full((n + 2 * GUARD,), sent, dtype=dtype, device=dev)
         self.t = self.buf[GUARD:GUARD + n].view(shape)
         if init is not None:
             self.t.copy_(init)
 
+    def is_sent(self, t):
+        """Elementwise: does t still hold the sentinel?"""
+        return torch.isnan(t) if self.sent != self.sent else t == self.sent
+
     def guards_intact(self):
-        return bool((self.buf[:GUARD] == SENT).all()) and bool((self.buf[self.buf.numel() - GUARD:] == SENT).all())
+        return bool(self.is_sent(self.buf[:GUARD]).all()) and bool(self.is_sent(self.buf[self.buf.numel() - GUARD:]).all())
 
     def untouched(self):
-        return bool((self.buf == SENT).all())
+        return bool(self.is_sent(self.buf).all())
 
     def cpu(self):
         return self.t.detach().cpu().clone()
