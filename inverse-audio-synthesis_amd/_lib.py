@@ -65,11 +65,12 @@ def _header_prototypes(header):
 
 
 # name -> (restype, argtypes), read from the declarations the kernel files are compiled against (csrc/ias_common.h
-# includes all three headers): the product ABI, the symbols only the diagnostic library exports, and the match report's
-# entry points (report.py), which both libraries export.
+# includes all four headers): the product ABI, the symbols only the diagnostic library exports, and the entry points of
+# the match report (report.py) and of the tied fit (match.py: tied_adam_step), which both libraries export.
 SYMBOLS = _header_prototypes("ias_hip.h")
 DIAG_SYMBOLS = _header_prototypes("ias_hip_diag.h")
 REPORT_SYMBOLS = _header_prototypes("ias_hip_report.h")
+TIED_SYMBOLS = _header_prototypes("ias_hip_tied.h")
 DIAG_LIB_PATH = os.path.join(_HERE, "csrc", "libias_hip_diag.so")
 
 _lib = None
@@ -90,7 +91,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C inverse-audio-synthesis_amd/csrc`.  There is no CPU fallback."
         )
-    _lib = _bind(_bind(ctypes.CDLL(LIB_PATH), SYMBOLS), REPORT_SYMBOLS)
+    _lib = _bind(_bind(_bind(ctypes.CDLL(LIB_PATH), SYMBOLS), REPORT_SYMBOLS), TIED_SYMBOLS)
     return _lib
 
 
@@ -113,7 +114,7 @@ def load_diag():
     if _diag is None:
         if not os.path.exists(DIAG_LIB_PATH):
             raise HipLibraryMissing(f"{DIAG_LIB_PATH} not found: `make -C inverse-audio-synthesis_amd/csrc`")
-        _diag = _bind(_bind(_bind(ctypes.CDLL(DIAG_LIB_PATH), SYMBOLS), REPORT_SYMBOLS), DIAG_SYMBOLS)
+        _diag = _bind(_bind(_bind(_bind(ctypes.CDLL(DIAG_LIB_PATH), SYMBOLS), REPORT_SYMBOLS), TIED_SYMBOLS), DIAG_SYMBOLS)
     return _diag
 
 

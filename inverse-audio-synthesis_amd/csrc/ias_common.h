@@ -45,6 +45,7 @@ constexpr bool kIasDiag = false;
 // another file's entry point needs no declaration of its own.  Relative to this file: no compile line needs an -I.
 #include "../../include/ias_hip.h"
 #include "../../include/ias_hip_report.h"
+#include "../../include/ias_hip_tied.h"
 #ifdef IAS_DIAG
 #include "../../include/ias_hip_diag.h"
 #endif

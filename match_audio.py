@@ -5,7 +5,8 @@
                           [--bank-batches NB] [--bank-stream CHUNK] [--evolve G] [--evolve-population M]
                           [--evolve-elites K] [--evolve-sigma S0] [--pitch] [--pitch-lo MIDI] [--pitch-hi MIDI]
                           [--envelope] [--envelope-generations G] [--envelope-population M]
-                          [--split] [--onset-delta D] [--max-notes K] [--fade-ms MS] [--loss LOSS] [--report]
+                          [--split] [--onset-delta D] [--max-notes K] [--fade-ms MS] [--shared] [--own M.N,M.N,...]
+                          [--loss LOSS] [--report]
                           [key=value ...]
 
 ``key=value`` are config overrides as for pretrain.py / audio_to_params.py (``torchsynth.rate``,
@@ -45,6 +46,15 @@ see the notes exactly as they see files.  Per input NAME the script writes NAME.
 note ``onset_sample``, ``onset_seconds``, ``length_samples``, ``strength``, ``gain`` and the fields of a params.json record)
 and NAME.match.wav at the file's full length: the best renders, each scaled by ``gain`` (the RMS of the target note over
 the RMS of its render) and put back at its onset (``onset.join_notes``).
+``--shared`` (off by default; needs ``--split``, one start per note) fits the notes of a file to ONE instrument.
+``--init``, ``--pitch``, ``--envelope`` and ``--evolve`` run per note as before; then the notes' starts are scored once under
+the matcher's loss, ``match.tie_starts`` gives every note of a file the best-scoring note's values in the tied columns, and
+``SoundMatcher.fit_tied`` fits the file's notes as a group: the columns named by ``--own module.name,...`` (default
+``keyboard.midi_f0,keyboard.duration``: the note and its length) stay per note, every other parameter is tied, one value
+per file, descending along the mean of the notes' gradients (``ias_match_tied_step``).  NAME.notes.json gains ``shared``
+({tied: the tied parameters' names, own, initial_group_loss, group_loss: the mean loss over the file's notes at the start
+and at the end}) and its notes agree in every tied column; NAME.preset.json holds the tied parameters once ({input, shared,
+params: ``params.json``-style rows}).
 ``--report`` (off by default) compares every best render with its target once after the fit, in figures that do not depend
 on ``--loss``: ``report.Reporter`` (the ``mel.*`` settings for its mel plan) gives ``lsd_db``, ``spectral_convergence``,
 ``logmel_l1_db``, ``mcd_db``, the counted ``frames`` and ``mel_frames``, ``envelope_db``, ``f0_cents`` (null where either side
@@ -208,6 +218,21 @@ def load_targets(args, files, rate, T, dev):
 
 
 INITS = ("center", "random", "bank")
+DEFAULT_OWN = "keyboard.midi_f0,keyboard.duration"   # ``match.DEFAULT_OWN`` as the flag spells it
+
+
+def parse_own(text):
+    """--own: "module.name,module.name,..." -> ((module, name), ...), each checked against ``voice_spec.PARAMS``
+    (ValueError naming the unknown one).  An empty string: no own columns."""
+    from inverse_audio_synthesis_amd import voice_spec as S
+    own = []
+    for item in (t.strip() for t in text.split(",") if t.strip()):
+        key = tuple(item.split(".", 1))
+        if key not in S.INDEX:
+            raise ValueError(f"unknown Voice parameter {item!r} (module.name, as in NAME.params.json)")
+        if key not in own:
+            own.append(key)
+    return tuple(own)
 BANK_BATCH = 128
 ENVELOPE_ELITES = 16                # ``envelope.fit_envelope``'s default
 
@@ -258,6 +283,11 @@ def parse_args(argv=None):
     ap.add_argument("--max-notes", type=int, default=256, metavar="K", help="--split: notes kept per file")
     ap.add_argument("--fade-ms", type=float, default=5.0, metavar="MS",
                     help="--split: linear fade-out of a note that is cut by the next onset or by the synth buffer")
+    ap.add_argument("--shared", action="store_true",
+                    help="--split: fit the notes of a file to one shared preset (SoundMatcher.fit_tied); only the --own "
+                         "columns differ from note to note; writes NAME.preset.json")
+    ap.add_argument("--own", default=DEFAULT_OWN, metavar="M.N,M.N,...",
+                    help="--shared: the parameters every note keeps for itself, as module.name")
     ap.add_argument("--report", action="store_true",
                     help="compare each best render with its target in loss-independent figures (report.Reporter) and "
                          "write them into every record and stdout line as `report`")
@@ -306,6 +336,15 @@ def parse_args(argv=None):
             ap.error("--bank-stream must be >= 1")
         if args.starts > 64:
             ap.error("--bank-stream keeps at most 64 starts per sound")
+    if args.shared:
+        if not args.split:
+            ap.error("--shared needs --split")
+        if args.starts > 1:
+            ap.error("--shared fits one start per note: --starts must be 1" + (" (with --evolve too)" if args.evolve else ""))
+    try:
+        args.own = parse_own(args.own)
+    except ValueError as e:
+        ap.error(f"--own: {e}")
     return args, files, overrides
 
 
@@ -393,6 +432,33 @@ def evolve_stage(args, stage, target, init, prov):
     return found.params01[:, :nS].contiguous() if nS > 1 else found.params01[:, 0].contiguous()
 
 
+def shared_stage(args, matcher, tg, init):
+    """--shared: score the notes' starts once under the matcher's loss, give every note of a file the best-scoring note's
+    tied columns and fit each file's notes as one group -> (a ``MatchResult`` of the notes for their records, the
+    ``shared`` block of every file)."""
+    from inverse_audio_synthesis_amd import voice_spec as S
+    from inverse_audio_synthesis_amd.match import MatchResult, tie_starts
+    init = written_out(init, tg.audio)
+    if init.dim() == 3:                              # --init bank: [N, 1, 78], the one start of every note
+        init = init[:, 0].contiguous()
+    tied = matcher.tied_mask(args.own)
+    score = matcher.fit(tg.audio, init_params01=init, steps=0).loss
+    init = tie_starts(init, tg.seg.row, tied, score)
+    res = matcher.fit_tied(tg.audio, tg.seg.row, init_params01=init, own=args.own, steps=args.steps, return_audio=True)
+    names = [f"{m}.{n}" for (m, n, *_r), t in zip(S.PARAMS, tied.tolist()) if t]
+    shared = [{"tied": names, "own": [f"{m}.{n}" for m, n in args.own], "initial_group_loss": a, "group_loss": b}
+              for a, b in zip(res.initial_group_loss.tolist(), res.group_loss.tolist())]
+    rows = tg.seg.row.long()
+    return MatchResult(params01=res.params01, loss=res.loss, initial_loss=res.initial_loss, skipped=res.skipped[rows],
+                       audio=res.audio), shared
+
+
+def preset_doc(name, shared, note):
+    """NAME.preset.json: the tied parameters once, as the ``params_record`` rows of one of the file's notes."""
+    tied = set(shared["tied"])
+    return {"input": name, "shared": shared, "params": [p for p in note["params"] if f"{p['module']}.{p['name']}" in tied]}
+
+
 def report_stage(cfg, rate, audio, target):
     """--report: the best renders against their targets -> one dict of ``report.MatchReport``'s fields per sound."""
     from inverse_audio_synthesis_amd.report import Reporter
@@ -440,9 +506,9 @@ def file_docs(args, files, rate, tg, res, prov, reports=None):
     return res.audio, docs, [{key: doc[key] for key in keys} for doc in docs]
 
 
-def notes_docs(args, files, rate, tg, res, prov, reports=None):
+def notes_docs(args, files, rate, tg, res, prov, reports=None, shared=None):
     """--split -> (the recordings [files, L] put together from the best renders, NAME.notes.json's content per file, its
-    stdout line per file)."""
+    stdout line per file); with --shared, ``shared[i]`` as file i's ``shared``."""
     from inverse_audio_synthesis_amd.onset import join_notes, note_gains
     seg = tg.seg
     gain = note_gains(seg.audio, res.audio, seg.length)
@@ -460,8 +526,13 @@ def notes_docs(args, files, rate, tg, res, prov, reports=None):
         docs.append({"input": os.path.basename(f), "rate": rate, "notes": notes})
         if args.resample:
             docs[i]["input_rate"] = int(tg.in_rates[i])
+        if shared is not None:
+            docs[i]["shared"] = shared[i]
     lines = [{"input": doc["input"], "notes": len(doc["notes"]), "final_loss": [n["final_loss"] for n in doc["notes"]]}
              for doc in docs]
+    if shared is not None:
+        for line, block in zip(lines, shared):
+            line["group_loss"] = block["group_loss"]
     if reports is not None:
         for line, doc in zip(lines, docs):
             line["report"] = [n["report"] for n in doc["notes"]]
@@ -479,6 +550,9 @@ def write_outputs(args, files, rate, tg, audio, docs, lines):
         name = os.path.splitext(os.path.basename(f))[0]
         with open(os.path.join(args.out, name + (".notes.json" if args.split else ".params.json")), "w") as fh:
             json.dump(docs[i], fh, indent=1)
+        if args.shared:
+            with open(os.path.join(args.out, name + ".preset.json"), "w") as fh:
+                json.dump(preset_doc(docs[i]["input"], docs[i]["shared"], docs[i]["notes"][0]), fh, indent=1)
         x = fit_length(host[i], tg.in_lengths[i], None) if args.split else host[i]
         write_wav(os.path.join(args.out, name + ".match.wav"), x, tg.in_rates[i])
         print(json.dumps(lines[i]), flush=True)
@@ -513,11 +587,17 @@ def main(argv=None):
         init = envelope_stage(args, tg.audio, rate, init, prov)
     if args.evolve > 0:
         init = evolve_stage(args, stage, tg.audio, init, prov)
-    res = matcher.fit(tg.audio, init_params01=init, steps=args.steps, return_audio=True)
+    shared = None
+    if args.shared:
+        res, shared = shared_stage(args, matcher, tg, init)
+    else:
+        res = matcher.fit(tg.audio, init_params01=init, steps=args.steps, return_audio=True)
     os.makedirs(args.out, exist_ok=True)
-    make_docs = notes_docs if args.split else file_docs
     reports = report_stage(cfg, rate, res.audio, tg.audio) if args.report else None
-    audio, docs, lines = make_docs(args, files, rate, tg, res, prov, reports)
+    if args.split:
+        audio, docs, lines = notes_docs(args, files, rate, tg, res, prov, reports, shared)
+    else:
+        audio, docs, lines = file_docs(args, files, rate, tg, res, prov, reports)
     write_outputs(args, files, rate, tg, audio, docs, lines)
 
 
