@@ -65,12 +65,14 @@ def _header_prototypes(header):
 
 
 # name -> (restype, argtypes), read from the declarations the kernel files are compiled against (csrc/ias_common.h
-# includes all four headers): the product ABI, the symbols only the diagnostic library exports, and the entry points of
-# the match report (report.py) and of the tied fit (match.py: tied_adam_step), which both libraries export.
+# includes all five headers): the product ABI, the symbols only the diagnostic library exports, and the entry points of
+# the match report (report.py), of the tied fit (match.py: tied_adam_step) and of the output gain (match.py: apply_gain,
+# solve_gain), which both libraries export.
 SYMBOLS = _header_prototypes("ias_hip.h")
 DIAG_SYMBOLS = _header_prototypes("ias_hip_diag.h")
 REPORT_SYMBOLS = _header_prototypes("ias_hip_report.h")
 TIED_SYMBOLS = _header_prototypes("ias_hip_tied.h")
+GAIN_SYMBOLS = _header_prototypes("ias_hip_gain.h")
 DIAG_LIB_PATH = os.path.join(_HERE, "csrc", "libias_hip_diag.so")
 
 _lib = None
@@ -91,7 +93,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C inverse-audio-synthesis_amd/csrc`.  There is no CPU fallback."
         )
-    _lib = _bind(_bind(_bind(ctypes.CDLL(LIB_PATH), SYMBOLS), REPORT_SYMBOLS), TIED_SYMBOLS)
+    _lib = _bind(_bind(_bind(_bind(ctypes.CDLL(LIB_PATH), SYMBOLS), REPORT_SYMBOLS), TIED_SYMBOLS), GAIN_SYMBOLS)
     return _lib
 
 
@@ -107,14 +109,17 @@ def load_diag():
     """The diagnostic build of the same sources (csrc/libias_hip_diag.so, -DIAS_DIAG: environment switches live,
     superseded kernels and ``ias_vicreg_set_form`` compiled in; include/ias_hip_diag.h).  The rule of the split is at the
     top of csrc/ias_common.h: what only a switch reaches is launched inside ``if constexpr (kIasDiag)``, so the product
-    library (257 kernels) holds no kernel its dispatch cannot reach and this one holds those and 39 more (296; the
+    library (262 kernels) holds no kernel its dispatch cannot reach and this one holds those and 39 more (301; the
     inventory is pinned by tests/test_capi_symbols.py).  A SEPARATE library instance:
     nothing the package does goes through it unless a test or a diagnostic script asks for it (``use_library``)."""
     global _diag
     if _diag is None:
         if not os.path.exists(DIAG_LIB_PATH):
             raise HipLibraryMissing(f"{DIAG_LIB_PATH} not found: `make -C inverse-audio-synthesis_amd/csrc`")
-        _diag = _bind(_bind(_bind(_bind(ctypes.CDLL(DIAG_LIB_PATH), SYMBOLS), REPORT_SYMBOLS), TIED_SYMBOLS), DIAG_SYMBOLS)
+        lib = ctypes.CDLL(DIAG_LIB_PATH)
+        for table in (SYMBOLS, REPORT_SYMBOLS, TIED_SYMBOLS, GAIN_SYMBOLS, DIAG_SYMBOLS):
+            _bind(lib, table)
+        _diag = lib
     return _diag
 
 

@@ -21,8 +21,8 @@
 //   dispatch sites  a launch, hipFuncSetAttribute or occupancy query that ONLY a diagnostic switch can reach stands inside
 //                   `if constexpr (kIasDiag) { ... }`, in one block in front of the product's choice, which follows as
 //                   straight-line code.  A discarded statement instantiates nothing: the product build compiles neither
-//                   the host stub nor the device code of a kernel template named only there: 257 kernels in the product
-//                   library, 296 in the diagnostic one (tests/test_capi_symbols.py holds the inventory; scripts/isa_diff.py
+//                   the host stub nor the device code of a kernel template named only there: 262 kernels in the product
+//                   library, 301 in the diagnostic one (tests/test_capi_symbols.py holds the inventory; scripts/isa_diff.py
 //                   compares two source trees kernel by kernel).
 //   ias_diag_env()  getenv in the diagnostic library, the constant NULL in the product library.  A switch that selects
 //                   between kernels the product also reaches by shape or alignment stays such a runtime read: both
@@ -46,6 +46,7 @@ constexpr bool kIasDiag = false;
 #include "../../include/ias_hip.h"
 #include "../../include/ias_hip_report.h"
 #include "../../include/ias_hip_tied.h"
+#include "../../include/ias_hip_gain.h"
 #ifdef IAS_DIAG
 #include "../../include/ias_hip_diag.h"
 #endif

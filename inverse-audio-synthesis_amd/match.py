@@ -21,6 +21,11 @@ the group's ``own`` columns (by default the note and its length).  Render, loss 
 each iteration walks all chunks, collects the rows' gradients and losses in [N, 78] and [N] buffers and ends in one
 ``ias_match_tied_step`` (include/ias_hip_tied.h) over all N rows: the mean gradient of a tied column over the group, one
 Adam update, the result written to every row.
+
+``gain="solved"`` / ``gain="fitted"`` (``fit`` and ``fit_tied``) add an output gain per sound, in dB, beside the 78
+parameters: the loss is taken on ``apply_gain(render, g)``, where g starts at the closed-form ``solve_gain`` of the target
+against the start's render and, when fitted, is the optimiser's 79th column (include/ias_hip_gain.h has the gain law and
+the three entry points).  The Voice and ``voice_spec.PARAMS`` know nothing of it.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -34,6 +39,9 @@ from .spectral import MelSpectrogramL1, MultiResolutionSTFTLoss, STFTL1
 
 LOSSES = ("mel_l1", "stft_l1", "multi_resolution_stft")
 DEFAULT_OWN = (("keyboard", "midi_f0"), ("keyboard", "duration"))   # fit_tied: what differs from note to note
+GAINS = (None, "solved", "fitted")
+GAIN_DB_LO, GAIN_DB_HI = -60.0, 20.0                 # the gain law of include/ias_hip_gain.h: g01 0 .. 1 is LO .. HI dB
+GAIN_UNITY01 = 0.75                                  # 0 dB, exact in fp32
 
 
 @dataclass
@@ -46,6 +54,8 @@ class MatchResult:
     start: Optional[torch.Tensor] = None   # [N] int64: the chosen start (init_params01 [N, S, 78] only)
     start_loss: Optional[torch.Tensor] = None            # [N, S] fp32: each start's final loss
     start_initial_loss: Optional[torch.Tensor] = None    # [N, S] fp32: each start's initial loss
+    gain_db: Optional[torch.Tensor] = None               # [N] fp32: the output gain of ``audio`` and ``loss`` (fit(gain=...))
+    initial_gain_db: Optional[torch.Tensor] = None       # [N] fp32: the gain the fit started from
 
 
 @dataclass
@@ -57,6 +67,8 @@ class TiedMatchResult:
     initial_group_loss: torch.Tensor    # [G] fp64
     skipped: torch.Tensor           # [G] int32: iterations a group skipped for a non-finite loss or gradient
     audio: Optional[torch.Tensor] = None   # [N, T] render of params01 (fit_tied(return_audio=True))
+    gain_db: Optional[torch.Tensor] = None               # [N] fp32: every note's output gain (fit_tied(gain=...))
+    initial_gain_db: Optional[torch.Tensor] = None       # [N] fp32
 
 
 def match_adam_step(params01, grad, m, v, step, loss, best_loss, best_params, free, active, skipped, lr, betas, eps):
@@ -151,6 +163,89 @@ def tie_starts(params01, groups, tied, score=None):
     return torch.where(tied.unsqueeze(0), params01[ref], params01)
 
 
+# ------------------------------------------------------------------------------------------------ output gain
+def gain01_from_db(db):
+    """dB (tensor) -> the gain column's value g01, fp32, clamped to GAIN_DB_LO .. GAIN_DB_HI (0 dB -> 0.75)."""
+    return ((db.double() - GAIN_DB_LO) / (GAIN_DB_HI - GAIN_DB_LO)).clamp(0.0, 1.0).float()
+
+
+def gain_db_from01(gain01):
+    """g01 (fp32 tensor) -> dB, fp32 (formed in fp64 as the kernels form it)."""
+    return (GAIN_DB_LO + (GAIN_DB_HI - GAIN_DB_LO) * gain01.double()).float()
+
+
+def _gain_rows(what, rows, vectors):
+    """The checks of the gain entry points: ``rows`` contiguous fp32 [B, T] of one shape, ``vectors`` contiguous fp32 [B]."""
+    shape = tuple(rows[0].shape)
+    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"{what}: expected [B, T] rows, got {shape}")
+    for t in rows:
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{what}: expected a contiguous float32 tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    for t in vectors:
+        if t.dtype != torch.float32 or tuple(t.shape) != shape[:1] or not t.is_contiguous():
+            raise ValueError(f"{what}: expected a contiguous float32 tensor of shape {shape[:1]}, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    return shape
+
+
+def _gain_partials(B, T, width, dev):
+    n = _lib.load().ias_gain_partials_count(T)
+    _lib.check(min(n, 0), "ias_gain_partials_count")
+    return torch.empty((B, n, width), dtype=torch.float64, device=dev)
+
+
+def gain_forward(audio, gain01):
+    """ias_gain_apply: audio [B, T], gain01 [B] -> a new [B, T] tensor a_b audio[b] (include/ias_hip_gain.h)."""
+    B, T = _gain_rows("gain_forward", (audio,), (gain01,))
+    out = torch.empty_like(audio)
+    st = _lib.load().ias_gain_apply(_lib.ptr(audio), _lib.ptr(gain01), _lib.ptr(out), B, T, _lib.stream())
+    _lib.check(st, "ias_gain_apply")
+    return out
+
+
+def gain_backward(g_out, audio, gain01):
+    """ias_gain_backward: the cotangent g_out [B, T] of ``gain_forward(audio, gain01)`` -> (g_audio [B, T], g_gain01 [B])."""
+    B, T = _gain_rows("gain_backward", (g_out, audio), (gain01,))
+    g_audio, g_gain01 = torch.empty_like(audio), torch.empty_like(gain01)
+    partials = _gain_partials(B, T, 1, audio.device)
+    st = _lib.load().ias_gain_backward(_lib.ptr(g_out), _lib.ptr(audio), _lib.ptr(gain01), _lib.ptr(g_audio),
+                                       _lib.ptr(g_gain01), _lib.ptr(partials), B, T, _lib.stream())
+    _lib.check(st, "ias_gain_backward")
+    return g_audio, g_gain01
+
+
+class _ApplyGain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, audio, gain01):
+        ctx.save_for_backward(audio, gain01)
+        return gain_forward(audio, gain01)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        audio, gain01 = ctx.saved_tensors
+        return gain_backward(g_out.contiguous(), audio, gain01)
+
+
+def apply_gain(audio, gain01):
+    """audio [B, T] fp32, gain01 [B] fp32 (g01 of the gain law: 0 .. 1 is -60 .. +20 dB, 0.75 is 0 dB) -> a_b audio[b] as a
+    new tensor, differentiable in both (ias_gain_apply / ias_gain_backward)."""
+    return _ApplyGain.apply(audio.contiguous(), gain01.contiguous())
+
+
+def solve_gain(target, render):
+    """target, render [B, T] fp32 -> g01 [B] fp32: the gain that gives ``render`` the energy of ``target``, clamped to the
+    range; 0.75 (0 dB) where either is silent or not finite (ias_gain_solve).  Not differentiable."""
+    target, render = target.detach().contiguous(), render.detach().contiguous()
+    B, T = _gain_rows("solve_gain", (target, render), ())
+    g01 = torch.empty(B, dtype=torch.float32, device=target.device)
+    partials = _gain_partials(B, T, 2, target.device)
+    st = _lib.load().ias_gain_solve(_lib.ptr(target), _lib.ptr(render), _lib.ptr(g01), _lib.ptr(partials), B, T,
+                                    _lib.stream())
+    _lib.check(st, "ias_gain_solve")
+    return g01
+
+
 class SoundMatcher:
     """Fit Voice parameters to target sounds by descent through the HIP render and a per-sound spectral loss.
 
@@ -198,7 +293,30 @@ class SoundMatcher:
         mel matcher's loss through ``evolve_search`` instead."""
         return evolve_search(self.voice, self.loss, target_audio=target_audio, frozen=self.frozen, **kw)
 
-    def fit(self, target_audio, init_params01=None, steps=200, return_audio=False):
+    def _gain_args(self, gain, init_gain_db, N):
+        """The ``gain`` and ``init_gain_db`` of ``fit`` / ``fit_tied``, checked -> the start's g01 [N] on the voice's
+        device (clamped to the range), or None: solve it."""
+        if gain not in GAINS:
+            raise ValueError(f"gain must be one of {GAINS}, got {gain!r}")
+        if init_gain_db is None:
+            return None
+        if gain is None:
+            raise ValueError("init_gain_db needs gain='solved' or gain='fitted'")
+        db = torch.as_tensor(init_gain_db).detach().to(device=self.voice.params01.device)
+        if tuple(db.shape) != (N,):
+            raise ValueError(f"init_gain_db must be [{N}] (dB, one per target), got {tuple(db.shape)}")
+        return gain01_from_db(db).contiguous()
+
+    def _render(self, q, gain=None, g=None):
+        """The audio the loss sees: q [B, 78] rendered and, with a gain, scaled by the fixed g [B] ("solved"); q [B, 79]:
+        the render of its first 78 columns scaled by its last ("fitted")."""
+        if gain is None:
+            return self.voice.render(q, normalize=True)
+        if gain == "fitted":
+            return apply_gain(self.voice.render(q[:, :S.NPARAMS].contiguous(), normalize=True), q[:, S.NPARAMS])
+        return apply_gain(self.voice.render(q, normalize=True), g)
+
+    def fit(self, target_audio, init_params01=None, steps=200, return_audio=False, gain=None, init_gain_db=None):
         """target_audio [N, T] (device, T == voice.synthconfig.buffer_size); init_params01 [N, 78] in 0..1 (None: 0.5)
         -> ``MatchResult``.  Targets go through in chunks of ``voice.batch_size``; the last chunk is padded with inactive
         rows (zero cotangent, never updated, not returned).
@@ -206,7 +324,16 @@ class SoundMatcher:
         Several starts per sound: init_params01 [N, S, 78].  The N S rows are fitted as one flattened [N S, 78] fit
         (row n S + s fits target n from start s) and, per sound, the start with the lowest final loss is kept (ties: the
         lowest s; ``retrieval.rank_distances``).  ``loss``, ``initial_loss``, ``skipped`` and ``audio`` are the chosen
-        start's; ``start``, ``start_loss`` and ``start_initial_loss`` say which and how every start ended."""
+        start's; ``start``, ``start_loss`` and ``start_initial_loss`` say which and how every start ended.
+
+        ``gain``: None (no gain: the [B, 78] path as it was), "solved" or "fitted".  With either, every sound has an
+        output gain g in dB (``GAIN_DB_LO`` .. ``GAIN_DB_HI``) and the loss is taken on ``apply_gain(render, g)``, in every
+        iteration, in the final pass and for ``steps=0``.  g starts at ``solve_gain(target, render of the start)``, or at
+        ``init_gain_db`` [N] (clamped to the range) where given.  "solved": g stays there.  "fitted": g is the 79th
+        column of the optimiser's state (free, whatever ``frozen`` says; clamped to the range by the step's clamp to
+        0 .. 1), and best-so-far covers all 79 columns.  Padded rows carry 0 dB.  ``params01`` stays [N, 78]; ``gain_db``
+        and ``initial_gain_db`` [N] are the returned and the starting gain, ``audio`` is the gained render and ``loss`` its
+        loss.  With several starts, ``init_gain_db`` [N] goes to every start of a sound."""
         voice = self.voice
         T = voice.synthconfig.buffer_size
         dev = voice.params01.device
@@ -217,39 +344,51 @@ class SoundMatcher:
             if init_params01.shape[0] != N or init_params01.shape[2] != S.NPARAMS or init_params01.shape[1] < 1:
                 raise ValueError(f"init_params01 must be [{N}, {S.NPARAMS}] or [{N}, starts, {S.NPARAMS}], got "
                                  f"{tuple(init_params01.shape)}")
-            return self._fit_starts(target_audio, init_params01, steps, return_audio)
+            g0 = self._gain_args(gain, init_gain_db, N)
+            return self._fit_starts(target_audio, init_params01, steps, return_audio, gain, g0)
         if init_params01 is None:
             init_params01 = torch.full((N, S.NPARAMS), 0.5, dtype=torch.float32, device=dev)
         if tuple(init_params01.shape) != (N, S.NPARAMS):
             raise ValueError(f"init_params01 must be [{N}, {S.NPARAMS}], got {tuple(init_params01.shape)}")
-        return self._fit_rows(target_audio, init_params01, steps, return_audio)
+        return self._fit_rows(target_audio, init_params01, steps, return_audio, gain, self._gain_args(gain, init_gain_db, N))
 
-    def _fit_rows(self, target_audio, init_params01, steps, return_audio):
+    def _fit_rows(self, target_audio, init_params01, steps, return_audio, gain=None, g0=None):
         voice = self.voice
         B, dev = voice.batch_size, voice.params01.device
         N = target_audio.shape[0]
         target_audio = target_audio.detach().to(device=dev, dtype=torch.float32)
         init_params01 = init_params01.detach().to(device=dev, dtype=torch.float32).clamp(0.0, 1.0)
-        outs = [self._fit_chunk(target_audio[s:s + B], init_params01[s:s + B], int(steps), return_audio)
+        outs = [self._fit_chunk(target_audio[s:s + B], init_params01[s:s + B], int(steps), return_audio, gain,
+                                None if g0 is None else g0[s:s + B])
                 for s in range(0, N, B)]
         cat = lambda i: torch.cat([o[i] for o in outs])     # noqa: E731
         return MatchResult(params01=cat(0), loss=cat(1), initial_loss=cat(2), skipped=cat(3),
-                           audio=cat(4) if return_audio else None)
+                           audio=cat(4) if return_audio else None, gain_db=None if gain is None else cat(5),
+                           initial_gain_db=None if gain is None else cat(6))
 
-    def _fit_starts(self, target_audio, init_params01, steps, return_audio):
+    def _fit_starts(self, target_audio, init_params01, steps, return_audio, gain=None, g0=None):
         from .retrieval import rank_distances
         N, nS = init_params01.shape[0], init_params01.shape[1]
         flat = self._fit_rows(target_audio.repeat_interleave(nS, dim=0), init_params01.reshape(N * nS, S.NPARAMS),
-                              steps, return_audio)
+                              steps, return_audio, gain, None if g0 is None else g0.repeat_interleave(nS))
         start_loss = flat.loss.reshape(N, nS)
         start = rank_distances(start_loss)[:, 0]
         rows = torch.arange(N, device=start.device) * nS + start
         pick = lambda t: None if t is None else t[rows]      # noqa: E731
         return MatchResult(params01=pick(flat.params01), loss=pick(flat.loss), initial_loss=pick(flat.initial_loss),
                            skipped=pick(flat.skipped), audio=pick(flat.audio), start=start, start_loss=start_loss,
-                           start_initial_loss=flat.initial_loss.reshape(N, nS))
+                           start_initial_loss=flat.initial_loss.reshape(N, nS), gain_db=pick(flat.gain_db),
+                           initial_gain_db=pick(flat.initial_gain_db))
 
-    def _fit_chunk(self, target, init, steps, return_audio):
+    def _start_gain(self, target, init, g0, n):
+        """The gain a chunk starts from -> g01 [B]: ``g0`` [n] padded with 0 dB, or ``solve_gain`` of the padded target
+        against the render of the padded start (a padded row's target is silence: 0 dB)."""
+        if g0 is not None:
+            return torch.cat([g0, g0.new_full((target.shape[0] - n,), GAIN_UNITY01)]).contiguous()
+        with torch.no_grad():
+            return solve_gain(target, self.voice.render(init.contiguous(), normalize=True))
+
+    def _fit_chunk(self, target, init, steps, return_audio, gain=None, g0=None):
         voice = self.voice
         B, n = voice.batch_size, target.shape[0]
         dev = target.device
@@ -261,6 +400,12 @@ class SoundMatcher:
         cot = active.to(torch.float32)
         with torch.no_grad():
             tgt = self.loss.target(target)
+        free, g = self.free, None
+        if gain is not None:
+            g = self._start_gain(target, init, g0, n)
+            if gain == "fitted":                     # the 79th column: one more free column of the same Adam step
+                init = torch.cat([init, g.unsqueeze(1)], dim=1)
+                free = torch.cat([free, free.new_ones(1)])
         p = init.clone().contiguous()
         m, v = torch.zeros_like(p), torch.zeros_like(p)
         step = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -270,21 +415,25 @@ class SoundMatcher:
         initial = None
         for _ in range(steps):
             q = p.clone().requires_grad_(True)
-            loss = self._per_item(voice.render(q, normalize=True), tgt)
+            loss = self._per_item(self._render(q, gain, g), tgt)
             if initial is None:
                 initial = loss.detach().clone()
             loss.backward(cot)
-            match_adam_step(p, q.grad, m, v, step, loss.detach(), best_loss, best_params, self.free, active, skipped,
+            match_adam_step(p, q.grad, m, v, step, loss.detach(), best_loss, best_params, free, active, skipped,
                             self.lr, self.betas, self.eps)
         with torch.no_grad():                        # the last parameters compete for "best" too
-            last = self._per_item(voice.render(p, normalize=True), tgt)
+            last = self._per_item(self._render(p, gain, g), tgt)
             if initial is None:
                 initial = last.clone()
             better = (active != 0) & (last.double() < best_loss)
             best_params = torch.where(better.unsqueeze(1), p, best_params)
             best_loss = torch.where(better, last.double(), best_loss)
-            audio = voice.render(best_params, normalize=True)[:n].clone() if return_audio else None
-        return best_params[:n], best_loss[:n].float(), initial[:n], skipped[:n], audio
+            audio = self._render(best_params, gain, g)[:n].clone() if return_audio else None
+        if gain is None:
+            return best_params[:n], best_loss[:n].float(), initial[:n], skipped[:n], audio
+        best_g = best_params[:, S.NPARAMS] if gain == "fitted" else g
+        return (best_params[:n, :S.NPARAMS].contiguous(), best_loss[:n].float(), initial[:n], skipped[:n], audio,
+                gain_db_from01(best_g[:n]), gain_db_from01(g[:n]))
 
     def tied_mask(self, own=DEFAULT_OWN):
         """-> [78] uint8 on the voice's device: 1 for the columns ``fit_tied`` ties, every non-frozen column that is not
@@ -315,19 +464,29 @@ class SoundMatcher:
         return chunks
 
     def _padded(self, p, s, n):
+        """Rows s .. s + n - 1 of p [N, 78 or 79] padded to a chunk: centre parameters and, in a gain column, 0 dB."""
         B = self.voice.batch_size
         rows = p[s:s + n]
-        return rows if n == B else torch.cat([rows, rows.new_full((B - n, S.NPARAMS), 0.5)])
+        if n == B:
+            return rows
+        pad = rows.new_full((B - n, p.shape[1]), 0.5)
+        pad[:, S.NPARAMS:] = GAIN_UNITY01
+        return torch.cat([rows, pad])
 
-    def _forward_all(self, chunks, p, loss_out, audio_out=None):
+    def _padded_gain(self, g, s, n):
+        B = self.voice.batch_size
+        return None if g is None else torch.cat([g[s:s + n], g.new_full((B - n,), GAIN_UNITY01)]).contiguous()
+
+    def _forward_all(self, chunks, p, loss_out, audio_out=None, gain=None, g=None):
         with torch.no_grad():
             for s, n, tgt, _cot in chunks:
-                audio = self.voice.render(self._padded(p, s, n).contiguous(), normalize=True)
+                audio = self._render(self._padded(p, s, n).contiguous(), gain, self._padded_gain(g, s, n))
                 loss_out[s:s + n] = self._per_item(audio, tgt)[:n]
                 if audio_out is not None:
                     audio_out[s:s + n] = audio[:n]
 
-    def fit_tied(self, target_audio, groups, init_params01=None, own=DEFAULT_OWN, steps=200, return_audio=False):
+    def fit_tied(self, target_audio, groups, init_params01=None, own=DEFAULT_OWN, steps=200, return_audio=False,
+                 gain=None, init_gain_db=None):
         """target_audio [N, T] as for ``fit``; groups [N]: non-decreasing integer group ids starting at 0 (``group_starts``:
         the one host check, before the loop; ValueError otherwise); init_params01 [N, 78] (None: 0.5) ->
         ``TiedMatchResult``.  The rows of a group are fitted as one instrument: every free column outside ``own`` is
@@ -338,7 +497,11 @@ class SoundMatcher:
         cotangent; the last chunk padded as in ``fit``), writes the chunk's gradient and loss into [N, 78] and [N]
         buffers and ends in one ``ias_match_tied_step`` over all N rows, so a group may cross chunks.  After the last
         iteration one forward pass lets the last parameters compete for best (``update=0``).  With one row per group
-        this is ``fit``, bit for bit."""
+        this is ``fit``, bit for bit.
+
+        ``gain`` and ``init_gain_db`` as for ``fit``: one output gain per NOTE, which is the note's velocity under tied
+        mixer levels.  "fitted": the arrays of the step are [N, 79] and the gain column is always an own column,
+        whatever ``own`` says."""
         voice = self.voice
         T = voice.synthconfig.buffer_size
         dev = voice.params01.device
@@ -351,12 +514,24 @@ class SoundMatcher:
             init_params01 = torch.full((N, S.NPARAMS), 0.5, dtype=torch.float32, device=dev)
         if tuple(init_params01.shape) != (N, S.NPARAMS):
             raise ValueError(f"init_params01 must be [{N}, {S.NPARAMS}], got {tuple(init_params01.shape)}")
-        tied = self.tied_mask(own)
+        tied, free = self.tied_mask(own), self.free
+        g0 = self._gain_args(gain, init_gain_db, N)
         ids = torch.as_tensor(groups).to(device=dev, dtype=torch.int64)
         target_audio = target_audio.detach().to(device=dev, dtype=torch.float32)
         init = init_params01.detach().to(device=dev, dtype=torch.float32).clamp(0.0, 1.0)
         p = tie_starts(init, ids, tied).contiguous()
         chunks = self._chunks(target_audio)
+        g = None
+        if gain is not None:
+            g = g0
+            if g is None:                            # per chunk as in ``fit``: the padded target against the padded start
+                B = voice.batch_size
+                g = torch.cat([self._start_gain(torch.cat([target_audio[s:s + n], target_audio.new_zeros((B - n, T))]),
+                                                self._padded(p, s, n), None, n)[:n] for s, n, _tgt, _cot in chunks])
+            if gain == "fitted":                     # the 79th column: free, and every note's own
+                p = torch.cat([p, g.unsqueeze(1)], dim=1).contiguous()
+                free = torch.cat([free, free.new_ones(1)])
+                tied = torch.cat([tied, tied.new_zeros(1)])
         m, v, grad = torch.zeros_like(p), torch.zeros_like(p), torch.zeros_like(p)
         loss = torch.zeros(N, dtype=torch.float32, device=dev)
         step = torch.zeros(G, dtype=torch.int32, device=dev)
@@ -368,25 +543,31 @@ class SoundMatcher:
         initial = initial_group = None
 
         def tied_step(update):
-            tied_adam_step(p, grad, m, v, best_params, loss, group_start, step, skipped, best_loss, group_loss, self.free,
+            tied_adam_step(p, grad, m, v, best_params, loss, group_start, step, skipped, best_loss, group_loss, free,
                            tied, active, update, self.lr, self.betas, self.eps)
 
         for _ in range(int(steps)):
             for s, n, tgt, cot in chunks:
                 q = self._padded(p, s, n).clone().requires_grad_(True)
-                rows = self._per_item(voice.render(q, normalize=True), tgt)
+                rows = self._per_item(self._render(q, gain, self._padded_gain(g, s, n)), tgt)
                 rows.backward(cot)
                 grad[s:s + n] = q.grad[:n]
                 loss[s:s + n] = rows.detach()[:n]
             tied_step(1)
             if initial is None:
                 initial, initial_group = loss.clone(), group_loss.clone()
-        self._forward_all(chunks, p, loss)           # the last parameters compete for "best" too
+        self._forward_all(chunks, p, loss, None, gain, g)        # the last parameters compete for "best" too
         tied_step(0)
         if initial is None:
             initial, initial_group = loss.clone(), group_loss.clone()
         audio = target_audio.new_zeros((N, T)) if return_audio else None
         final = torch.zeros_like(loss)
-        self._forward_all(chunks, best_params, final, audio)
+        self._forward_all(chunks, best_params, final, audio, gain, g)
+        gain_db = initial_gain_db = None
+        if gain is not None:
+            initial_gain_db = gain_db_from01(g)
+            gain_db = gain_db_from01(best_params[:, S.NPARAMS]) if gain == "fitted" else initial_gain_db
+            best_params = best_params[:, :S.NPARAMS].contiguous()
         return TiedMatchResult(params01=best_params, loss=final, group_loss=best_loss, initial_loss=initial,
-                               initial_group_loss=initial_group, skipped=skipped, audio=audio)
+                               initial_group_loss=initial_group, skipped=skipped, audio=audio, gain_db=gain_db,
+                               initial_gain_db=initial_gain_db)

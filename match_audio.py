@@ -6,7 +6,7 @@
                           [--evolve-elites K] [--evolve-sigma S0] [--pitch] [--pitch-lo MIDI] [--pitch-hi MIDI]
                           [--envelope] [--envelope-generations G] [--envelope-population M]
                           [--split] [--onset-delta D] [--max-notes K] [--fade-ms MS] [--shared] [--own M.N,M.N,...]
-                          [--loss LOSS] [--report]
+                          [--gain solved|fitted] [--loss LOSS] [--report]
                           [key=value ...]
 
 ``key=value`` are config overrides as for pretrain.py / audio_to_params.py (``torchsynth.rate``,
@@ -55,6 +55,16 @@ per file, descending along the mean of the notes' gradients (``ias_match_tied_st
 ({tied: the tied parameters' names, own, initial_group_loss, group_loss: the mean loss over the file's notes at the start
 and at the end}) and its notes agree in every tied column; NAME.preset.json holds the tied parameters once ({input, shared,
 params: ``params.json``-style rows}).
+``--gain solved|fitted`` (off by default) handles the recording's level as a quantity of its own: every sound (every note
+under ``--split``) gets an output gain in dB between -60 and +20, and the loss is taken on the render scaled by it
+(``match.apply_gain``), so a quiet take is not paid for with the mixer levels and the envelopes' sustain.  The gain starts
+at the closed-form ``match.solve_gain`` of the target against the render of the start the stages before produced; ``solved``
+keeps it there, ``fitted`` makes it the 79th column of the same Adam step.  Under ``--shared`` it is per note (the note's
+velocity beside tied mixer levels), and the scoring call that picks the reference note is level-matched too.  Every record
+gains ``gain_mode``, ``initial_gain_db`` and ``fit_gain_db``; NAME.match.wav and ``--report`` use the gained render; the
+``gain`` of a note under ``--split`` is then the RMS ratio against the gained render; NAME.preset.json is unchanged (the gain
+is the note's).  The search stages (``--init bank``, ``--evolve``) score their candidates as before, at the synth's own
+level: level-matched scoring there is left for a later change.
 ``--report`` (off by default) compares every best render with its target once after the fit, in figures that do not depend
 on ``--loss``: ``report.Reporter`` (the ``mel.*`` settings for its mel plan) gives ``lsd_db``, ``spectral_convergence``,
 ``logmel_l1_db``, ``mcd_db``, the counted ``frames`` and ``mel_frames``, ``envelope_db``, ``f0_cents`` (null where either side
@@ -288,6 +298,9 @@ def parse_args(argv=None):
                          "columns differ from note to note; writes NAME.preset.json")
     ap.add_argument("--own", default=DEFAULT_OWN, metavar="M.N,M.N,...",
                     help="--shared: the parameters every note keeps for itself, as module.name")
+    ap.add_argument("--gain", choices=("solved", "fitted"), default=None,
+                    help="an output gain in dB per sound beside the 78 parameters: solved in closed form against the "
+                         "start's render (solved) and then fitted by the same Adam step (fitted)")
     ap.add_argument("--report", action="store_true",
                     help="compare each best render with its target in loss-independent figures (report.Reporter) and "
                          "write them into every record and stdout line as `report`")
@@ -442,15 +455,16 @@ def shared_stage(args, matcher, tg, init):
     if init.dim() == 3:                              # --init bank: [N, 1, 78], the one start of every note
         init = init[:, 0].contiguous()
     tied = matcher.tied_mask(args.own)
-    score = matcher.fit(tg.audio, init_params01=init, steps=0).loss
+    score = matcher.fit(tg.audio, init_params01=init, steps=0, gain=args.gain).loss     # --gain: ranked level-matched
     init = tie_starts(init, tg.seg.row, tied, score)
-    res = matcher.fit_tied(tg.audio, tg.seg.row, init_params01=init, own=args.own, steps=args.steps, return_audio=True)
+    res = matcher.fit_tied(tg.audio, tg.seg.row, init_params01=init, own=args.own, steps=args.steps, return_audio=True,
+                           gain=args.gain)
     names = [f"{m}.{n}" for (m, n, *_r), t in zip(S.PARAMS, tied.tolist()) if t]
     shared = [{"tied": names, "own": [f"{m}.{n}" for m, n in args.own], "initial_group_loss": a, "group_loss": b}
               for a, b in zip(res.initial_group_loss.tolist(), res.group_loss.tolist())]
     rows = tg.seg.row.long()
     return MatchResult(params01=res.params01, loss=res.loss, initial_loss=res.initial_loss, skipped=res.skipped[rows],
-                       audio=res.audio), shared
+                       audio=res.audio, gain_db=res.gain_db, initial_gain_db=res.initial_gain_db), shared
 
 
 def preset_doc(name, shared, note):
@@ -473,6 +487,9 @@ def record(args, res, prov, i, name, reports=None):
     rec = {"input": name, "loss_kind": args.loss, "steps": args.steps,
            "initial_loss": float(res.initial_loss[i]), "final_loss": float(res.loss[i]),
            "skipped": int(res.skipped[i]), "init": args.init, "params": params_record(res.params01[i])}
+    if args.gain is not None:
+        rec["gain_mode"] = args.gain
+        rec["initial_gain_db"], rec["fit_gain_db"] = float(res.initial_gain_db[i]), float(res.gain_db[i])
     s = 0
     if res.start is not None:
         s = rec["start"] = int(res.start[i])
@@ -591,7 +608,7 @@ def main(argv=None):
     if args.shared:
         res, shared = shared_stage(args, matcher, tg, init)
     else:
-        res = matcher.fit(tg.audio, init_params01=init, steps=args.steps, return_audio=True)
+        res = matcher.fit(tg.audio, init_params01=init, steps=args.steps, return_audio=True, gain=args.gain)
     os.makedirs(args.out, exist_ok=True)
     reports = report_stage(cfg, rate, res.audio, tg.audio) if args.report else None
     if args.split:
