@@ -43,15 +43,17 @@ SENT, GUARD = -777.0, 64
 class Guarded:
     """A device tensor `t` of `shape` inside a 1-D buffer with GUARD sentinels on each side (and sentinels in it until it is
     written): what a kernel stores outside its output, or does not store at all, stays visible.  `sent`: the sentinel
-    (NaN for a kernel's INPUTS: a read outside the payload that enters arithmetic poisons the result)."""
+    (NaN for a kernel's INPUTS: a read outside the payload that enters arithmetic poisons the result).  `offset`: `t` starts
+    that many elements later (the front guard grows by them), for a payload that is not aligned as the allocation is."""
 
-    def __init__(self, dev, shape, init=None, dtype=torch.float32, sent=SENT):
+    def __init__(self, dev, shape, init=None, dtype=torch.float32, sent=SENT, offset=0):
         n = 1
         for d in shape:
             n *= d
         self.sent = sent
-        self.buf = torch.full((n + 2 * GUARD,), sent, dtype=dtype, device=dev)
-        self.t = self.buf[GUARD:GUARD + n].view(shape)
+        self.lo, self.hi = GUARD + offset, GUARD + offset + n
+        self.buf = torch.full((n + 2 * GUARD + offset,), sent, dtype=dtype, device=dev)
+        self.t = self.buf[self.lo:self.hi].view(shape)
         if init is not None:
             self.t.copy_(init)
 
@@ -60,7 +62,7 @@ class Guarded:
         return torch.isnan(t) if self.sent != self.sent else t == self.sent
 
     def guards_intact(self):
-        return bool(self.is_sent(self.buf[:GUARD]).all()) and bool(self.is_sent(self.buf[self.buf.numel() - GUARD:]).all())
+        return bool(self.is_sent(self.buf[:self.lo]).all()) and bool(self.is_sent(self.buf[self.hi:]).all())
 
     def untouched(self):
         return bool(self.is_sent(self.buf).all())
