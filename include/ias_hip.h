@@ -311,8 +311,9 @@ int ias_l1_grad(const float* x, const float* y, const float* g_loss, float scale
  * skipped [B] int32; loss [B] fp32 = the loss of params as they are; best_loss [B] fp64; free_cols [P], active [B]
  * uint8).  For each active row: loss < best_loss -> best_params = params, best_loss = loss; then, if the loss or a free
  * column's gradient is not finite, skipped += 1 and nothing else changes; otherwise step += 1 and torch.optim.Adam's
- * update (bias corrections of that row's step) on the free columns, clamped to [0, 1].  Frozen columns and inactive rows
- * are left as they are. */
+ * update (bias corrections of that row's step) on the free columns, clamped to [0, 1]: the fp32 expressions, with their
+ * three fused multiply-adds, are written out under ias_match_tied_step (ias_hip_tied.h), whose kernel shares the device
+ * function (csrc/match_step_kernels.hip).  Frozen columns and inactive rows are left as they are. */
 int ias_l1_rows_partials_count(long long n);
 int ias_l1_rows(const float* values, const float* target, int B, long long n, double* partials, float* out, void* stream);
 int ias_stft_loss_backward_rows(const float* audio, const float* window, const float* tables, const int* mel_start,

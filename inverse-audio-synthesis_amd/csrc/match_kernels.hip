@@ -1,5 +1,5 @@
-// Sound matching (MI355X / gfx950): the per-sound L1 of two spectrogram tensors and the per-sound Adam update of the
-// matcher (inverse-audio-synthesis_amd/match.py).
+// Sound matching (MI355X / gfx950): the per-sound losses of the matcher (inverse-audio-synthesis_amd/match.py), the L1 of
+// two spectrogram tensors and the MR-STFT sums, a value per row.
 //
 // The reference's inverse loop -- params -> synth -> mel-L1 against the true audio -- is the commented-out block
 // /root/reference/audio_to_params.py:56-172; its notebook wants one candidate and one distance per test sound
@@ -18,7 +18,7 @@
 //   loss kernels (spectral_kernels.hip, LOSS2: fmaf for the squares, the difference of two __log2f, ln 2 applied to the
 //   row's sum); the fold is a wave per row.  mrstft_rows_total_kernel / mrstft_coef_rows_kernel: mrstft_total_kernel /
 //   mrstft_coef_kernel (spectral_grad_kernels.hip) once per row.
-// match_adam_kernel: one 64-lane workgroup per row; see ias_match_adam_step below.
+// The optimiser steps (match_adam_kernel, match_tied_kernel) are in match_step_kernels.hip.
 #include "ias_common.h"
 #include <cstdint>
 
@@ -231,72 +231,6 @@ __global__ __launch_bounds__(256) void mrstft_coef_rows_kernel(const double* __r
   coef[2 * (size_t)b + 1] = g / ((double)nres * count);
 }
 
-// ------------------------------------------------------------------------------------------------ per-row Adam
-// torch.optim.Adam's step (no weight decay, no amsgrad) with a step counter per row, the best-so-far bookkeeping of the
-// matcher and a row skip on non-finite input.  Lane k owns columns k and k + 64 (P <= 128) from the load to the store,
-// so the copy to best_params reads the parameters before this update writes them.
-#define ADAM_THREADS 64
-#define ADAM_MAX_P (2 * ADAM_THREADS)
-
-__global__ __launch_bounds__(ADAM_THREADS) void match_adam_kernel(float* __restrict__ params, const float* __restrict__ grad,
-                                                                  float* __restrict__ m, float* __restrict__ v,
-                                                                  int* __restrict__ step, const float* __restrict__ loss,
-                                                                  double* __restrict__ best_loss,
-                                                                  float* __restrict__ best_params,
-                                                                  const unsigned char* __restrict__ free_cols,
-                                                                  const unsigned char* __restrict__ active,
-                                                                  int* __restrict__ skipped, int P, float lr, float beta1,
-                                                                  float beta2, float eps) {
-  const int b = blockIdx.x, k = threadIdx.x;
-  if (!active[b]) return;                              // uniform over the workgroup
-  const size_t row = (size_t)b * P;
-  const float lb = loss[b];
-  const double best = best_loss[b];
-  const int t_prev = step[b];
-  bool bad = !isfinite(lb);
-  float p[2], g[2];
-  bool fr[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int c = k + u * ADAM_THREADS;
-    fr[u] = c < P && free_cols[c] != 0;
-    p[u] = c < P ? params[row + c] : 0.0f;
-    g[u] = fr[u] ? grad[row + c] : 0.0f;
-    if (fr[u] && !isfinite(g[u])) bad = true;
-  }
-  // every lane has read best_loss / step before lane 0 writes them
-  const bool skip = __syncthreads_or(bad) != 0;
-  if ((double)lb < best) {                             // strict: a tie keeps the earlier parameters
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int c = k + u * ADAM_THREADS;
-      if (c < P) best_params[row + c] = p[u];
-    }
-    if (k == 0) best_loss[b] = (double)lb;
-  }
-  if (skip) {
-    if (k == 0) skipped[b] += 1;
-    return;
-  }
-  const int t = t_prev + 1;
-  const float bc1 = (float)(1.0 - pow((double)beta1, (double)t));
-  const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)t));
-  const float step_size = lr / bc1;
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    if (!fr[u]) continue;
-    const size_t i = row + k + u * ADAM_THREADS;
-    const float mi = m[i] + (1.0f - beta1) * (g[u] - m[i]);        // exp_avg.lerp_(grad, 1 - beta1)
-    const float vi = v[i] * beta2 + (1.0f - beta2) * g[u] * g[u];  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    const float pn = p[u] - step_size * (mi / denom);
-    m[i] = mi;
-    v[i] = vi;
-    params[i] = fminf(fmaxf(pn, 0.0f), 1.0f);
-  }
-  if (k == 0) step[b] = t;
-}
-
 // ------------------------------------------------------------------------------------------------ C ABI
 extern "C" int ias_l1_rows_partials_count(long long n) {
   if (n <= 0 || (n + L1R_CHUNK - 1) / L1R_CHUNK > 2147483647LL) return IAS_ERR_ARG;
@@ -348,19 +282,5 @@ extern "C" int ias_mrstft_coef_rows(const double* sums, const float* g_rows, dou
   if (!sums || !g_rows || !coef || nres < 1 || nres > MRR_MAX_RES || B <= 0 || !(count > 0.0)) return IAS_ERR_ARG;
   hipLaunchKernelGGL(mrstft_coef_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream_, sums, g_rows, count,
                      nres, B, coef);
-  return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
-}
-
-extern "C" int ias_match_adam_step(float* params, const float* grad, float* m, float* v, int* step, const float* loss,
-                                   double* best_loss, float* best_params, const unsigned char* free_cols,
-                                   const unsigned char* active, int* skipped, int B, int P, float lr, float beta1,
-                                   float beta2, float eps, void* stream_) {
-  if (!params || !grad || !m || !v || !step || !loss || !best_loss || !best_params || !free_cols || !active || !skipped)
-    return IAS_ERR_ARG;
-  if (B <= 0 || P <= 0 || P > ADAM_MAX_P) return IAS_ERR_ARG;
-  if (!(lr >= 0.0f) || !(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f) || !(eps > 0.0f))
-    return IAS_ERR_ARG;
-  hipLaunchKernelGGL(match_adam_kernel, dim3(B), dim3(ADAM_THREADS), 0, (hipStream_t)stream_, params, grad, m, v, step, loss,
-                     best_loss, best_params, free_cols, active, skipped, P, lr, beta1, beta2, eps);
   return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
 }

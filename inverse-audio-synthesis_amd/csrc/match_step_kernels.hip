@@ -1,6 +1,18 @@
-// Tied sound matching (MI355X / gfx950): the grouped optimiser step of SoundMatcher.fit_tied
-// (inverse-audio-synthesis_amd/match.py; match_audio.py --shared).  The contract is in include/ias_hip_tied.h.
+// Sound matching (MI355X / gfx950): the optimiser steps of the matcher (inverse-audio-synthesis_amd/match.py), the per-row
+// one of SoundMatcher.fit (ias_match_adam_step, include/ias_hip.h) and the grouped one of SoundMatcher.fit_tied and
+// match_audio.py --shared (ias_match_tied_step, include/ias_hip_tied.h).
 //
+// Both are torch.optim.Adam's step (no weight decay, no amsgrad) on columns clamped to [0, 1], with a step counter, the
+// best-so-far bookkeeping and a skip on non-finite input per row or per group.  What they share is written once:
+// adam_step_const (the bias corrections of step t), adam_update (one column: p, m, v, g -> p', m', v') and adam_hyper_ok
+// (the host's check of lr, beta1, beta2, eps).  adam_update names its three fused multiply-adds as fmaf and this file is
+// built with -ffp-contract=off (the Makefile's EXACT_FP list), so every rounding of an update is in the source and the
+// two kernels give a row the same bits whatever surrounds the call; with singleton groups the two entry points agree bit
+// for bit (tests/test_tied_gpu.py::test_singleton_groups_are_the_untied_step_bit_for_bit), and
+// tests/test_match_step_bits_gpu.py holds both to recorded results.
+//
+// match_adam_kernel: one 64-lane workgroup per row.  Lane k owns columns k and k + 64 (P <= 128) from the load to the
+//   store, so the copy to best_params reads the parameters before this update writes them.
 // match_tied_kernel: one workgroup of TIED_THREADS = 128 lanes per group, lane c on column c (P <= 128) of EVERY row of
 //   the group from its first load to its last store.  A row is read as P consecutive floats by P consecutive lanes; the
 //   row-order fp64 sum of a column's gradients is a loop in one lane, TIED_BATCH rows' loads issued ahead of their adds.
@@ -10,32 +22,97 @@
 //   barrier also orders every lane's read of best_loss[g] and step[g] before lane 0 writes them.
 //   A workgroup walks its rows in three passes (gradients, best copy when better, update): the rows of one group are a few
 //   hundred KB at most and the second and third pass find them in the cache.
-//
-// The update of one column is written once (tied_adam_update), with the roundings of match_adam_kernel
-// (match_kernels.hip) spelled out.  That file is built with hipcc's default contraction, which fuses three of its
-// multiplies into the adds behind them; WHICH multiply of v beta2 + ((1 - beta2) g) g it fuses depends on the code around
-// the expression (the same source line in this kernel came out fused the other way round and differed in the last bit
-// of v).  So this file is built with -ffp-contract=off (the Makefile's EXACT_FP list) and names the three fused
-// operations match_adam_kernel's ISA has as fmaf: with singleton groups the two entry points give the same bits, and
-// tests/test_tied_gpu.py::test_singleton_groups_are_the_untied_step_bit_for_bit fails if a compiler ever contracts
-// match_adam_kernel differently.
 #include "ias_common.h"
 
+#define ADAM_THREADS 64
+#define ADAM_MAX_P (2 * ADAM_THREADS)
 #define TIED_THREADS 128
 #define TIED_MAX_P TIED_THREADS
 #define TIED_BATCH 8
 
-struct TiedStepConst { float beta1, beta2, eps, bc2_sqrt, step_size; };
+struct AdamStepConst { float beta1, beta2, eps, bc2_sqrt, step_size; };
 
-// match_adam_kernel's arithmetic for one column: (p, m, v, g) -> the new p, m and v
-__device__ __forceinline__ void tied_adam_update(float& p, float& m, float& v, float g, const TiedStepConst& k) {
-  const float mi = fmaf(1.0f - k.beta1, g - m, m);                    // m + (1 - beta1) (g - m), one rounding
-  const float vi = fmaf(g, (1.0f - k.beta2) * g, v * k.beta2);        // v beta2 + ((1 - beta2) g) g: the last product fused
+// step t (>= 1) of a row or group: bc1 = fp32(1 - beta1^t), bc2_sqrt = fp32(sqrt(1 - beta2^t)) (pow and sqrt in fp64)
+__device__ __forceinline__ AdamStepConst adam_step_const(int t, float lr, float beta1, float beta2, float eps) {
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)t));
+  AdamStepConst k;
+  k.beta1 = beta1;
+  k.beta2 = beta2;
+  k.eps = eps;
+  k.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)t));
+  k.step_size = lr / bc1;
+  return k;
+}
+
+// one column: exp_avg.lerp_(grad, 1 - beta1), exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2), the step, the clamp.
+// Three fused multiply-adds with one rounding each; every other operation rounds to fp32 on its own.
+__device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g, const AdamStepConst& k) {
+  const float mi = fmaf(1.0f - k.beta1, g - m, m);                    // m + (1 - beta1) (g - m)
+  const float vi = fmaf(g, (1.0f - k.beta2) * g, v * k.beta2);        // v beta2 + ((1 - beta2) g) g
   const float denom = sqrtf(vi) / k.bc2_sqrt + k.eps;
-  const float pn = fmaf(-k.step_size, mi / denom, p);                 // p - step_size (m' / denom), one rounding
+  const float pn = fmaf(-k.step_size, mi / denom, p);                 // p - step_size (m' / denom)
   m = mi;
   v = vi;
   p = fminf(fmaxf(pn, 0.0f), 1.0f);
+}
+
+static bool adam_hyper_ok(float lr, float beta1, float beta2, float eps) {
+  return lr >= 0.0f && beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f && eps > 0.0f;
+}
+
+__global__ __launch_bounds__(ADAM_THREADS) void match_adam_kernel(float* __restrict__ params, const float* __restrict__ grad,
+                                                                  float* __restrict__ m, float* __restrict__ v,
+                                                                  int* __restrict__ step, const float* __restrict__ loss,
+                                                                  double* __restrict__ best_loss,
+                                                                  float* __restrict__ best_params,
+                                                                  const unsigned char* __restrict__ free_cols,
+                                                                  const unsigned char* __restrict__ active,
+                                                                  int* __restrict__ skipped, int P, float lr, float beta1,
+                                                                  float beta2, float eps) {
+  const int b = blockIdx.x, k = threadIdx.x;
+  if (!active[b]) return;                              // uniform over the workgroup
+  const size_t row = (size_t)b * P;
+  const float lb = loss[b];
+  const double best = best_loss[b];
+  const int t_prev = step[b];
+  bool bad = !isfinite(lb);
+  float p[2], g[2];
+  bool fr[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int c = k + u * ADAM_THREADS;
+    fr[u] = c < P && free_cols[c] != 0;
+    p[u] = c < P ? params[row + c] : 0.0f;
+    g[u] = fr[u] ? grad[row + c] : 0.0f;
+    if (fr[u] && !isfinite(g[u])) bad = true;
+  }
+  // every lane has read best_loss / step before lane 0 writes them
+  const bool skip = __syncthreads_or(bad) != 0;
+  if ((double)lb < best) {                             // strict: a tie keeps the earlier parameters
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int c = k + u * ADAM_THREADS;
+      if (c < P) best_params[row + c] = p[u];
+    }
+    if (k == 0) best_loss[b] = (double)lb;
+  }
+  if (skip) {
+    if (k == 0) skipped[b] += 1;
+    return;
+  }
+  const int t = t_prev + 1;
+  const AdamStepConst sc = adam_step_const(t, lr, beta1, beta2, eps);
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    if (!fr[u]) continue;
+    const size_t i = row + k + u * ADAM_THREADS;
+    float pi = p[u], mi = m[i], vi = v[i];
+    adam_update(pi, mi, vi, g[u], sc);
+    m[i] = mi;
+    v[i] = vi;
+    params[i] = pi;
+  }
+  if (k == 0) step[b] = t;
 }
 
 __global__ __launch_bounds__(TIED_THREADS) void match_tied_kernel(
@@ -118,17 +195,11 @@ __global__ __launch_bounds__(TIED_THREADS) void match_tied_kernel(
     return;
   }
   const int t = t_prev + 1;
-  const float bc1 = (float)(1.0 - pow((double)beta1, (double)t));
-  TiedStepConst k;
-  k.beta1 = beta1;
-  k.beta2 = beta2;
-  k.eps = eps;
-  k.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)t));
-  k.step_size = lr / bc1;
+  const AdamStepConst k = adam_step_const(t, lr, beta1, beta2, eps);
   if (tied) {
     const size_t base = (size_t)r0 * P + c;
     float pi = params[base], mi = m[base], vi = v[base];
-    tied_adam_update(pi, mi, vi, (float)(gsum / (double)n), k);
+    adam_update(pi, mi, vi, (float)(gsum / (double)n), k);
     for (int r = 0; r < n; ++r) {
       const size_t i = base + (size_t)r * P;
       m[i] = mi;
@@ -152,7 +223,7 @@ __global__ __launch_bounds__(TIED_THREADS) void match_tied_kernel(
       for (int u = 0; u < TIED_BATCH; ++u) {
         if (r + u < n) {
           const size_t i = base + (size_t)(r + u) * P;
-          tied_adam_update(pv[u], mv[u], vv[u], gv[u], k);
+          adam_update(pv[u], mv[u], vv[u], gv[u], k);
           m[i] = mv[u];
           v[i] = vv[u];
           params[i] = pv[u];
@@ -164,6 +235,19 @@ __global__ __launch_bounds__(TIED_THREADS) void match_tied_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
+extern "C" int ias_match_adam_step(float* params, const float* grad, float* m, float* v, int* step, const float* loss,
+                                   double* best_loss, float* best_params, const unsigned char* free_cols,
+                                   const unsigned char* active, int* skipped, int B, int P, float lr, float beta1,
+                                   float beta2, float eps, void* stream_) {
+  if (!params || !grad || !m || !v || !step || !loss || !best_loss || !best_params || !free_cols || !active || !skipped)
+    return IAS_ERR_ARG;
+  if (B <= 0 || P <= 0 || P > ADAM_MAX_P) return IAS_ERR_ARG;
+  if (!adam_hyper_ok(lr, beta1, beta2, eps)) return IAS_ERR_ARG;
+  hipLaunchKernelGGL(match_adam_kernel, dim3(B), dim3(ADAM_THREADS), 0, (hipStream_t)stream_, params, grad, m, v, step, loss,
+                     best_loss, best_params, free_cols, active, skipped, P, lr, beta1, beta2, eps);
+  return hipGetLastError() == hipSuccess ? IAS_OK : IAS_ERR_LAUNCH;
+}
+
 extern "C" int ias_match_tied_step(float* params, const float* grad, float* m, float* v, float* best_params,
                                    const float* loss, const int* group_start, int* step, int* skipped, double* best_loss,
                                    double* group_loss, const unsigned char* free_cols, const unsigned char* tied_cols,
@@ -173,8 +257,7 @@ extern "C" int ias_match_tied_step(float* params, const float* grad, float* m, f
       !group_loss || !free_cols || !tied_cols || !active)
     return IAS_ERR_ARG;
   if (N < 1 || G < 1 || G > N || P < 1 || (update != 0 && update != 1)) return IAS_ERR_ARG;
-  if (!(lr >= 0.0f) || !(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f) || !(eps > 0.0f))
-    return IAS_ERR_ARG;
+  if (!adam_hyper_ok(lr, beta1, beta2, eps)) return IAS_ERR_ARG;
   if (P > TIED_MAX_P || G > 65535) return IAS_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(match_tied_kernel, dim3(G), dim3(TIED_THREADS), 0, (hipStream_t)stream_, params, grad, m, v,
                      best_params, loss, group_start, step, skipped, best_loss, group_loss, free_cols, tied_cols, active, N,

@@ -4,7 +4,9 @@ This closes the loop the reference left commented out (/root/reference/audio_to_
 mel-L1 against the true audio) as a product feature, and returns what its notebook wanted in the end
 (/root/reference/evaluate_audio_representations.py:202-231): a candidate and a distance per target sound.
 
-Per chunk of ``voice.batch_size`` targets, every iteration is
+``fit`` and ``fit_tied`` are one descent routine (``SoundMatcher._descend``) with two optimiser steps.  It owns the padding
+of its rows to whole chunks of ``voice.batch_size``, the state, the iterations, the final pass in which the last
+parameters compete for best, and the gain column.  Per chunk, every iteration is
 
     audio = voice.render(p)                      HIP render with its adjoint (voice_grad.py), normalize=True
     L     = loss.per_item(audio, target)         [B] per-sound spectral L1 or MR-STFT (spectral.py, csrc/match_kernels.hip)
@@ -12,14 +14,16 @@ Per chunk of ``voice.batch_size`` targets, every iteration is
                                                  ias_stft_loss_backward_rows, ias_mrstft_coef_rows + the *_mrstft_rows
                                                  span / frame kernels): a sound's gradient does not depend on the
                                                  batch, padded rows get exactly 0
-    ias_match_adam_step                          best-so-far, non-finite skip, Adam per row, clamp to [0, 1]
 
-with all state on the device and no host read inside the loop.
+and then one step over all its rows: ``ias_match_adam_step`` (best-so-far, non-finite skip, Adam per row, clamp to
+[0, 1]) or ``ias_match_tied_step`` (csrc/match_step_kernels.hip), with all state on the device and no host read inside
+the loop.  ``fit`` hands the routine one chunk at a time, all its steps, so that one chunk's loss target is alive at once;
+the step then reads the chunk's gradient and loss where backward left them.
 
 ``fit_tied`` fits the notes of a phrase to ONE instrument: the rows of a group share every free column that is not one of
-the group's ``own`` columns (by default the note and its length).  Render, loss and backward are the per-row ones above;
-each iteration walks all chunks, collects the rows' gradients and losses in [N, 78] and [N] buffers and ends in one
-``ias_match_tied_step`` (include/ias_hip_tied.h) over all N rows: the mean gradient of a tied column over the group, one
+the group's ``own`` columns (by default the note and its length).  It hands the routine all N rows: each iteration walks
+all chunks, collects the rows' gradients and losses in [rows, 78] and [rows] buffers and ends in one
+``ias_match_tied_step`` (include/ias_hip_tied.h) over the N rows: the mean gradient of a tied column over the group, one
 Adam update, the result written to every row.
 
 ``gain="solved"`` / ``gain="fitted"`` (``fit`` and ``fit_tied``) add an output gain per sound, in dB, beside the 78
@@ -71,17 +75,36 @@ class TiedMatchResult:
     initial_gain_db: Optional[torch.Tensor] = None       # [N] fp32
 
 
+@dataclass
+class _Descent:
+    """What ``SoundMatcher._descend`` leaves, over its rows padded to whole chunks."""
+    best_params: torch.Tensor       # [rows, 78 or 79 (gain="fitted": the gain column)]
+    best_loss: torch.Tensor         # [rows] or [G] fp64
+    skipped: torch.Tensor           # [rows] or [G] int32
+    chunks: list                    # per chunk (its rows as a slice, the loss's target, cotangent [B], views of p and g)
+    gain: Optional[str]
+    gain01: Optional[torch.Tensor]  # [rows]: the gain the descent started from (and, "solved", kept)
+    initial_loss: Optional[torch.Tensor] = None          # [rows] fp32
+    group_loss: Optional[torch.Tensor] = None            # [G] fp64 (tied): the last step's
+    initial_group_loss: Optional[torch.Tensor] = None    # [G] fp64 (tied)
+
+
+def _check_arrays(what, table):
+    """The argument check of the step wrappers: ``table`` of (tensor, dtype, shape), each to be contiguous."""
+    for t, dt, shape in table:
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{what}: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+
+
 def match_adam_step(params01, grad, m, v, step, loss, best_loss, best_params, free, active, skipped, lr, betas, eps):
     """One launch of ias_match_adam_step over [B, P] (see include/ias_hip.h).  Updates params01, m, v, step, best_loss,
     best_params and skipped in place."""
     B, P = params01.shape
-    for t, dt, shape in ((params01, torch.float32, (B, P)), (grad, torch.float32, (B, P)), (m, torch.float32, (B, P)),
-                         (v, torch.float32, (B, P)), (best_params, torch.float32, (B, P)), (step, torch.int32, (B,)),
-                         (loss, torch.float32, (B,)), (best_loss, torch.float64, (B,)), (free, torch.uint8, (P,)),
-                         (active, torch.uint8, (B,)), (skipped, torch.int32, (B,))):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f"match_adam_step: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} "
-                             f"{tuple(t.shape)}")
+    f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+    _check_arrays("match_adam_step", ((params01, f32, (B, P)), (grad, f32, (B, P)), (m, f32, (B, P)), (v, f32, (B, P)),
+                                      (best_params, f32, (B, P)), (step, i32, (B,)), (loss, f32, (B,)),
+                                      (best_loss, torch.float64, (B,)), (free, u8, (P,)), (active, u8, (B,)),
+                                      (skipped, i32, (B,))))
     st = _lib.load().ias_match_adam_step(
         _lib.ptr(params01), _lib.ptr(grad), _lib.ptr(m), _lib.ptr(v), _lib.ptr(step), _lib.ptr(loss), _lib.ptr(best_loss),
         _lib.ptr(best_params), _lib.ptr(free), _lib.ptr(active), _lib.ptr(skipped), B, P, float(lr), float(betas[0]),
@@ -95,14 +118,11 @@ def tied_adam_step(params01, grad, m, v, best_params, loss, group_start, step, s
     v, step, best_loss, best_params, group_loss and skipped in place; ``update`` False: the best-so-far pass alone."""
     N, P = params01.shape
     G = step.shape[0]
-    for t, dt, shape in ((params01, torch.float32, (N, P)), (grad, torch.float32, (N, P)), (m, torch.float32, (N, P)),
-                         (v, torch.float32, (N, P)), (best_params, torch.float32, (N, P)), (loss, torch.float32, (N,)),
-                         (group_start, torch.int32, (G + 1,)), (step, torch.int32, (G,)), (skipped, torch.int32, (G,)),
-                         (best_loss, torch.float64, (G,)), (group_loss, torch.float64, (G,)), (free, torch.uint8, (P,)),
-                         (tied, torch.uint8, (P,)), (active, torch.uint8, (G,))):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f"tied_adam_step: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} "
-                             f"{tuple(t.shape)}")
+    f32, i32, f64, u8 = torch.float32, torch.int32, torch.float64, torch.uint8
+    _check_arrays("tied_adam_step", ((params01, f32, (N, P)), (grad, f32, (N, P)), (m, f32, (N, P)), (v, f32, (N, P)),
+                                     (best_params, f32, (N, P)), (loss, f32, (N,)), (group_start, i32, (G + 1,)),
+                                     (step, i32, (G,)), (skipped, i32, (G,)), (best_loss, f64, (G,)),
+                                     (group_loss, f64, (G,)), (free, u8, (P,)), (tied, u8, (P,)), (active, u8, (G,))))
     if update not in (0, 1, False, True):
         raise ValueError(f"tied_adam_step: update must be 0 or 1, got {update!r}")
     st = _lib.load().ias_match_tied_step(
@@ -316,6 +336,25 @@ class SoundMatcher:
             return apply_gain(self.voice.render(q[:, :S.NPARAMS].contiguous(), normalize=True), q[:, S.NPARAMS])
         return apply_gain(self.voice.render(q, normalize=True), g)
 
+    def _fit_inputs(self, target_audio, init_params01, starts=False, groups=None):
+        """The checks ``fit`` and ``fit_tied`` share -> (N, init_params01 or the centre, ``group_starts(groups, N)`` on the
+        voice's device or None).  ``starts``: init_params01 may be [N, starts, 78]."""
+        T, dev = self.voice.synthconfig.buffer_size, self.voice.params01.device
+        if target_audio.dim() != 2 or target_audio.shape[1] != T:
+            raise ValueError(f"target_audio must be [N, {T}] (the voice's buffer), got {tuple(target_audio.shape)}")
+        N = target_audio.shape[0]
+        group_start = None if groups is None else group_starts(groups, N).to(dev)
+        if starts and init_params01 is not None and init_params01.dim() == 3:
+            if init_params01.shape[0] != N or init_params01.shape[2] != S.NPARAMS or init_params01.shape[1] < 1:
+                raise ValueError(f"init_params01 must be [{N}, {S.NPARAMS}] or [{N}, starts, {S.NPARAMS}], got "
+                                 f"{tuple(init_params01.shape)}")
+            return N, init_params01, group_start
+        if init_params01 is None:
+            init_params01 = torch.full((N, S.NPARAMS), 0.5, dtype=torch.float32, device=dev)
+        if tuple(init_params01.shape) != (N, S.NPARAMS):
+            raise ValueError(f"init_params01 must be [{N}, {S.NPARAMS}], got {tuple(init_params01.shape)}")
+        return N, init_params01, group_start
+
     def fit(self, target_audio, init_params01=None, steps=200, return_audio=False, gain=None, init_gain_db=None):
         """target_audio [N, T] (device, T == voice.synthconfig.buffer_size); init_params01 [N, 78] in 0..1 (None: 0.5)
         -> ``MatchResult``.  Targets go through in chunks of ``voice.batch_size``; the last chunk is padded with inactive
@@ -334,23 +373,10 @@ class SoundMatcher:
         0 .. 1), and best-so-far covers all 79 columns.  Padded rows carry 0 dB.  ``params01`` stays [N, 78]; ``gain_db``
         and ``initial_gain_db`` [N] are the returned and the starting gain, ``audio`` is the gained render and ``loss`` its
         loss.  With several starts, ``init_gain_db`` [N] goes to every start of a sound."""
-        voice = self.voice
-        T = voice.synthconfig.buffer_size
-        dev = voice.params01.device
-        if target_audio.dim() != 2 or target_audio.shape[1] != T:
-            raise ValueError(f"target_audio must be [N, {T}] (the voice's buffer), got {tuple(target_audio.shape)}")
-        N = target_audio.shape[0]
-        if init_params01 is not None and init_params01.dim() == 3:
-            if init_params01.shape[0] != N or init_params01.shape[2] != S.NPARAMS or init_params01.shape[1] < 1:
-                raise ValueError(f"init_params01 must be [{N}, {S.NPARAMS}] or [{N}, starts, {S.NPARAMS}], got "
-                                 f"{tuple(init_params01.shape)}")
-            g0 = self._gain_args(gain, init_gain_db, N)
-            return self._fit_starts(target_audio, init_params01, steps, return_audio, gain, g0)
-        if init_params01 is None:
-            init_params01 = torch.full((N, S.NPARAMS), 0.5, dtype=torch.float32, device=dev)
-        if tuple(init_params01.shape) != (N, S.NPARAMS):
-            raise ValueError(f"init_params01 must be [{N}, {S.NPARAMS}], got {tuple(init_params01.shape)}")
-        return self._fit_rows(target_audio, init_params01, steps, return_audio, gain, self._gain_args(gain, init_gain_db, N))
+        N, init_params01, _ = self._fit_inputs(target_audio, init_params01, starts=True)
+        g0 = self._gain_args(gain, init_gain_db, N)
+        run = self._fit_starts if init_params01.dim() == 3 else self._fit_rows
+        return run(target_audio, init_params01, steps, return_audio, gain, g0)
 
     def _fit_rows(self, target_audio, init_params01, steps, return_audio, gain=None, g0=None):
         voice = self.voice
@@ -380,60 +406,117 @@ class SoundMatcher:
                            start_initial_loss=flat.initial_loss.reshape(N, nS), gain_db=pick(flat.gain_db),
                            initial_gain_db=pick(flat.initial_gain_db))
 
-    def _start_gain(self, target, init, g0, n):
-        """The gain a chunk starts from -> g01 [B]: ``g0`` [n] padded with 0 dB, or ``solve_gain`` of the padded target
-        against the render of the padded start (a padded row's target is silence: 0 dB)."""
-        if g0 is not None:
-            return torch.cat([g0, g0.new_full((target.shape[0] - n,), GAIN_UNITY01)]).contiguous()
-        with torch.no_grad():
-            return solve_gain(target, self.voice.render(init.contiguous(), normalize=True))
-
     def _fit_chunk(self, target, init, steps, return_audio, gain=None, g0=None):
-        voice = self.voice
-        B, n = voice.batch_size, target.shape[0]
-        dev = target.device
-        active = torch.zeros(B, dtype=torch.uint8, device=dev)
-        active[:n] = 1
-        if n < B:                                    # padded rows: silence against centre parameters
-            target = torch.cat([target, target.new_zeros((B - n, target.shape[1]))])
-            init = torch.cat([init, init.new_full((B - n, S.NPARAMS), 0.5)])
-        cot = active.to(torch.float32)
-        with torch.no_grad():
-            tgt = self.loss.target(target)
-        free, g = self.free, None
+        """One chunk of ``fit``, all its steps: what leaves this frame holds no loss target, so one chunk's is alive at a
+        time (an MR-STFT target of the flagship shapes is over a gigabyte)."""
+        n = target.shape[0]
+        d = self._descend(target, init, steps, gain, g0)
+        audio = None
+        if return_audio:
+            audio = target.new_zeros(target.shape)
+            self._forward(d, d.best_params, audio_out=audio)
+        return (d.best_params[:n, :S.NPARAMS], d.best_loss[:n].float(), d.initial_loss[:n], d.skipped[:n], audio,
+                *self._gain_db(d, n))
+
+    def _descend(self, target, init, steps, gain=None, g0=None, tied=None):
+        """The descent under ``fit`` and ``fit_tied``: target [n, T] and init [n, 78] on the device (n >= 1 rows: a chunk
+        of ``fit``, all rows of ``fit_tied``), g0 [n] or None -> ``_Descent``.  All state is padded to whole chunks of
+        ``voice.batch_size`` rows once: centre parameters, 0 dB, silence targets, rows that are inactive (untied) or in no
+        group (tied: the step sees the first n rows alone).  A row keeps its place in its chunk, which fixes its noise.
+        ``tied``: None, the per-row ``match_adam_step``, or (group_start [G + 1], tied mask [78]), ``tied_adam_step``;
+        nothing else differs.  An iteration is, per chunk, the clone of its parameters, render, loss and backward, then
+        one step; with one chunk the step reads q.grad and the loss themselves, with several they are collected in
+        [rows, P] and [rows] buffers.  The last parameters compete for best in a final forward (the step's best-so-far
+        pass alone).  No host read."""
+        B, n, dev = self.voice.batch_size, target.shape[0], target.device
+        M = -(-n // B) * B
+        real = torch.arange(M, device=dev) < n
+        if n < M:
+            target = torch.cat([target, target.new_zeros((M - n, target.shape[1]))])
+            init = torch.cat([init, init.new_full((M - n, S.NPARAMS), 0.5)])
+        spans = [slice(s, s + B) for s in range(0, M, B)]
+        free, mask, g = self.free, None if tied is None else tied[1], None
         if gain is not None:
-            g = self._start_gain(target, init, g0, n)
-            if gain == "fitted":                     # the 79th column: one more free column of the same Adam step
+            if g0 is not None:
+                g = torch.cat([g0, g0.new_full((M - n,), GAIN_UNITY01)]).contiguous()
+            else:                                    # per chunk: the padded target against the padded start (silence: 0 dB)
+                with torch.no_grad():
+                    g = torch.cat([solve_gain(target[rows], self.voice.render(init[rows].contiguous(), normalize=True))
+                                   for rows in spans])
+            if gain == "fitted":                     # the 79th column: free, and under ``fit_tied`` every note's own
                 init = torch.cat([init, g.unsqueeze(1)], dim=1)
                 free = torch.cat([free, free.new_ones(1)])
+                mask = None if mask is None else torch.cat([mask, mask.new_zeros(1)])
         p = init.clone().contiguous()
-        m, v = torch.zeros_like(p), torch.zeros_like(p)
-        step = torch.zeros(B, dtype=torch.int32, device=dev)
-        skipped = torch.zeros(B, dtype=torch.int32, device=dev)
-        best_loss = torch.full((B,), float("inf"), dtype=torch.float64, device=dev)
-        best_params = p.clone()
-        initial = None
+        cot = real.to(torch.float32)
+        with torch.no_grad():                        # per chunk: its rows, loss target, cotangent and views of its p and g
+            chunks = [(rows, self.loss.target(target[rows]), cot[rows], p[rows], None if g is None else g[rows])
+                      for rows in spans]
+        m, v, best_params = torch.zeros_like(p), torch.zeros_like(p), p.clone()
+        K = M if tied is None else tied[0].shape[0] - 1          # counters: per row, or per group
+        step = torch.zeros(K, dtype=torch.int32, device=dev)
+        skipped = torch.zeros(K, dtype=torch.int32, device=dev)
+        best_loss = torch.full((K,), float("inf"), dtype=torch.float64, device=dev)
+        d = _Descent(best_params, best_loss, skipped, chunks, gain, g)
+        if tied is None:
+            active = real.to(torch.uint8)
+
+            def take_step(grad, loss, update):
+                if update:
+                    return match_adam_step(p, grad, m, v, step, loss, best_loss, best_params, free, active, skipped,
+                                           self.lr, self.betas, self.eps)
+                better = real & (loss.double() < best_loss)
+                best_params.copy_(torch.where(better.unsqueeze(1), p, best_params))
+                best_loss.copy_(torch.where(better, loss.double(), best_loss))
+        else:
+            active = torch.ones(K, dtype=torch.uint8, device=dev)
+            d.group_loss = torch.zeros(K, dtype=torch.float64, device=dev)
+
+            def take_step(grad, loss, update):
+                tied_adam_step(p[:n], grad[:n], m[:n], v[:n], best_params[:n], loss[:n], tied[0], step, skipped, best_loss,
+                               d.group_loss, free, mask, active, update, self.lr, self.betas, self.eps)
+
+        def started(loss):
+            if d.initial_loss is None:
+                d.initial_loss = loss.clone()
+                d.initial_group_loss = None if tied is None else d.group_loss.clone()
+
+        grad, loss = torch.zeros_like(p), torch.zeros(M, dtype=torch.float32, device=dev)
         for _ in range(steps):
-            q = p.clone().requires_grad_(True)
-            loss = self._per_item(self._render(q, gain, g), tgt)
-            if initial is None:
-                initial = loss.detach().clone()
-            loss.backward(cot)
-            match_adam_step(p, q.grad, m, v, step, loss.detach(), best_loss, best_params, free, active, skipped,
-                            self.lr, self.betas, self.eps)
-        with torch.no_grad():                        # the last parameters compete for "best" too
-            last = self._per_item(self._render(p, gain, g), tgt)
-            if initial is None:
-                initial = last.clone()
-            better = (active != 0) & (last.double() < best_loss)
-            best_params = torch.where(better.unsqueeze(1), p, best_params)
-            best_loss = torch.where(better, last.double(), best_loss)
-            audio = self._render(best_params, gain, g)[:n].clone() if return_audio else None
-        if gain is None:
-            return best_params[:n], best_loss[:n].float(), initial[:n], skipped[:n], audio
-        best_g = best_params[:, S.NPARAMS] if gain == "fitted" else g
-        return (best_params[:n, :S.NPARAMS].contiguous(), best_loss[:n].float(), initial[:n], skipped[:n], audio,
-                gain_db_from01(best_g[:n]), gain_db_from01(g[:n]))
+            for rows, tgt, c, p_rows, g_rows in chunks:
+                q = p_rows.clone().requires_grad_(True)
+                rows_loss = self._per_item(self._render(q, gain, g_rows), tgt)
+                rows_loss.backward(c)
+                if len(chunks) == 1:
+                    grad, loss = q.grad, rows_loss.detach()
+                else:
+                    grad[rows], loss[rows] = q.grad, rows_loss.detach()
+            take_step(grad, loss, 1)
+            started(loss)
+        last = torch.zeros(M, dtype=torch.float32, device=dev)
+        self._forward(d, p, last)                    # the last parameters compete for "best" too
+        take_step(grad, last, 0)
+        started(last)
+        return d
+
+    def _forward(self, d, p, loss_out=None, audio_out=None):
+        """Render p [rows of ``d``, 78 or 79] chunk by chunk with ``d``'s gain -> the rows' losses into loss_out and their
+        audio into audio_out (either None: not wanted), as many rows as each holds."""
+        with torch.no_grad():
+            for rows, tgt, _cot, _p, g_rows in d.chunks:
+                audio = self._render(p[rows].contiguous(), d.gain, g_rows)
+                if loss_out is not None:             # an output shorter than the padded rows ends inside the last chunk
+                    loss_out[rows] = self._per_item(audio, tgt)[:loss_out[rows].shape[0]]
+                if audio_out is not None:
+                    audio_out[rows] = audio[:audio_out[rows].shape[0]]
+
+    @staticmethod
+    def _gain_db(d, n):
+        """-> (gain_db, initial_gain_db) [n] of a descent's best parameters and of its start; (None, None) without a gain."""
+        if d.gain is None:
+            return None, None
+        best = d.best_params[:n, S.NPARAMS] if d.gain == "fitted" else d.gain01[:n]
+        return gain_db_from01(best), gain_db_from01(d.gain01[:n])
 
     def tied_mask(self, own=DEFAULT_OWN):
         """-> [78] uint8 on the voice's device: 1 for the columns ``fit_tied`` ties, every non-frozen column that is not
@@ -447,44 +530,6 @@ class SoundMatcher:
             mask[[S.INDEX[k] for k in own]] = 0
         return mask
 
-    def _chunks(self, target_audio):
-        """The chunks of ``voice.batch_size`` rows of [N, T] targets -> [(first row, rows, the loss's target of the chunk
-        padded with silence, its cotangent [B]: 1 for a row, 0 for padding)]."""
-        B, N = self.voice.batch_size, target_audio.shape[0]
-        chunks = []
-        for s in range(0, N, B):
-            target = target_audio[s:s + B]
-            n = target.shape[0]
-            if n < B:                                # padded rows: silence against centre parameters, as in _fit_chunk
-                target = torch.cat([target, target.new_zeros((B - n, target.shape[1]))])
-            cot = torch.zeros(B, dtype=torch.float32, device=target.device)
-            cot[:n] = 1.0
-            with torch.no_grad():
-                chunks.append((s, n, self.loss.target(target), cot))
-        return chunks
-
-    def _padded(self, p, s, n):
-        """Rows s .. s + n - 1 of p [N, 78 or 79] padded to a chunk: centre parameters and, in a gain column, 0 dB."""
-        B = self.voice.batch_size
-        rows = p[s:s + n]
-        if n == B:
-            return rows
-        pad = rows.new_full((B - n, p.shape[1]), 0.5)
-        pad[:, S.NPARAMS:] = GAIN_UNITY01
-        return torch.cat([rows, pad])
-
-    def _padded_gain(self, g, s, n):
-        B = self.voice.batch_size
-        return None if g is None else torch.cat([g[s:s + n], g.new_full((B - n,), GAIN_UNITY01)]).contiguous()
-
-    def _forward_all(self, chunks, p, loss_out, audio_out=None, gain=None, g=None):
-        with torch.no_grad():
-            for s, n, tgt, _cot in chunks:
-                audio = self._render(self._padded(p, s, n).contiguous(), gain, self._padded_gain(g, s, n))
-                loss_out[s:s + n] = self._per_item(audio, tgt)[:n]
-                if audio_out is not None:
-                    audio_out[s:s + n] = audio[:n]
-
     def fit_tied(self, target_audio, groups, init_params01=None, own=DEFAULT_OWN, steps=200, return_audio=False,
                  gain=None, init_gain_db=None):
         """target_audio [N, T] as for ``fit``; groups [N]: non-decreasing integer group ids starting at 0 (``group_starts``:
@@ -493,81 +538,26 @@ class SoundMatcher:
         TIED, one value per group, which moves along the mean of the rows' gradients; the ``own`` columns stay per row.
         A start whose rows disagree in a tied column takes the group's first row there (``tie_starts``).
 
-        Each iteration walks all chunks of ``voice.batch_size`` rows (render, ``per_item``, ``backward`` with the active
-        cotangent; the last chunk padded as in ``fit``), writes the chunk's gradient and loss into [N, 78] and [N]
-        buffers and ends in one ``ias_match_tied_step`` over all N rows, so a group may cross chunks.  After the last
-        iteration one forward pass lets the last parameters compete for best (``update=0``).  With one row per group
-        this is ``fit``, bit for bit.
+        The descent is ``fit``'s (``_descend``) over all N rows at once: each iteration walks all chunks of
+        ``voice.batch_size`` rows (the last one padded as in ``fit``) and ends in one ``ias_match_tied_step`` over the N
+        rows, so a group may cross chunks.  With one row per group this is ``fit``, bit for bit.  ``loss`` and ``audio``
+        are a fresh forward of the best parameters.
 
         ``gain`` and ``init_gain_db`` as for ``fit``: one output gain per NOTE, which is the note's velocity under tied
         mixer levels.  "fitted": the arrays of the step are [N, 79] and the gain column is always an own column,
         whatever ``own`` says."""
-        voice = self.voice
-        T = voice.synthconfig.buffer_size
-        dev = voice.params01.device
-        if target_audio.dim() != 2 or target_audio.shape[1] != T:
-            raise ValueError(f"target_audio must be [N, {T}] (the voice's buffer), got {tuple(target_audio.shape)}")
-        N = target_audio.shape[0]
-        group_start = group_starts(groups, N).to(dev)
-        G = group_start.shape[0] - 1
-        if init_params01 is None:
-            init_params01 = torch.full((N, S.NPARAMS), 0.5, dtype=torch.float32, device=dev)
-        if tuple(init_params01.shape) != (N, S.NPARAMS):
-            raise ValueError(f"init_params01 must be [{N}, {S.NPARAMS}], got {tuple(init_params01.shape)}")
-        tied, free = self.tied_mask(own), self.free
+        dev = self.voice.params01.device
+        N, init_params01, group_start = self._fit_inputs(target_audio, init_params01, groups=groups)
+        tied = self.tied_mask(own)
         g0 = self._gain_args(gain, init_gain_db, N)
         ids = torch.as_tensor(groups).to(device=dev, dtype=torch.int64)
         target_audio = target_audio.detach().to(device=dev, dtype=torch.float32)
         init = init_params01.detach().to(device=dev, dtype=torch.float32).clamp(0.0, 1.0)
-        p = tie_starts(init, ids, tied).contiguous()
-        chunks = self._chunks(target_audio)
-        g = None
-        if gain is not None:
-            g = g0
-            if g is None:                            # per chunk as in ``fit``: the padded target against the padded start
-                B = voice.batch_size
-                g = torch.cat([self._start_gain(torch.cat([target_audio[s:s + n], target_audio.new_zeros((B - n, T))]),
-                                                self._padded(p, s, n), None, n)[:n] for s, n, _tgt, _cot in chunks])
-            if gain == "fitted":                     # the 79th column: free, and every note's own
-                p = torch.cat([p, g.unsqueeze(1)], dim=1).contiguous()
-                free = torch.cat([free, free.new_ones(1)])
-                tied = torch.cat([tied, tied.new_zeros(1)])
-        m, v, grad = torch.zeros_like(p), torch.zeros_like(p), torch.zeros_like(p)
-        loss = torch.zeros(N, dtype=torch.float32, device=dev)
-        step = torch.zeros(G, dtype=torch.int32, device=dev)
-        skipped = torch.zeros(G, dtype=torch.int32, device=dev)
-        active = torch.ones(G, dtype=torch.uint8, device=dev)
-        best_loss = torch.full((G,), float("inf"), dtype=torch.float64, device=dev)
-        group_loss = torch.zeros(G, dtype=torch.float64, device=dev)
-        best_params = p.clone()
-        initial = initial_group = None
-
-        def tied_step(update):
-            tied_adam_step(p, grad, m, v, best_params, loss, group_start, step, skipped, best_loss, group_loss, free,
-                           tied, active, update, self.lr, self.betas, self.eps)
-
-        for _ in range(int(steps)):
-            for s, n, tgt, cot in chunks:
-                q = self._padded(p, s, n).clone().requires_grad_(True)
-                rows = self._per_item(self._render(q, gain, self._padded_gain(g, s, n)), tgt)
-                rows.backward(cot)
-                grad[s:s + n] = q.grad[:n]
-                loss[s:s + n] = rows.detach()[:n]
-            tied_step(1)
-            if initial is None:
-                initial, initial_group = loss.clone(), group_loss.clone()
-        self._forward_all(chunks, p, loss, None, gain, g)        # the last parameters compete for "best" too
-        tied_step(0)
-        if initial is None:
-            initial, initial_group = loss.clone(), group_loss.clone()
-        audio = target_audio.new_zeros((N, T)) if return_audio else None
-        final = torch.zeros_like(loss)
-        self._forward_all(chunks, best_params, final, audio, gain, g)
-        gain_db = initial_gain_db = None
-        if gain is not None:
-            initial_gain_db = gain_db_from01(g)
-            gain_db = gain_db_from01(best_params[:, S.NPARAMS]) if gain == "fitted" else initial_gain_db
-            best_params = best_params[:, :S.NPARAMS].contiguous()
-        return TiedMatchResult(params01=best_params, loss=final, group_loss=best_loss, initial_loss=initial,
-                               initial_group_loss=initial_group, skipped=skipped, audio=audio, gain_db=gain_db,
-                               initial_gain_db=initial_gain_db)
+        d = self._descend(target_audio, tie_starts(init, ids, tied), int(steps), gain, g0, tied=(group_start, tied))
+        final = torch.zeros(N, dtype=torch.float32, device=dev)
+        audio = target_audio.new_zeros(target_audio.shape) if return_audio else None
+        self._forward(d, d.best_params, final, audio)
+        gain_db, initial_gain_db = self._gain_db(d, N)
+        return TiedMatchResult(params01=d.best_params[:N, :S.NPARAMS].contiguous(), loss=final, group_loss=d.best_loss,
+                               initial_loss=d.initial_loss[:N], initial_group_loss=d.initial_group_loss, skipped=d.skipped,
+                               audio=audio, gain_db=gain_db, initial_gain_db=initial_gain_db)

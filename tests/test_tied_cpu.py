@@ -26,10 +26,12 @@ def test_tied_symbols_and_prototype():
 
 def test_tied_kernel_file_is_compiled_against_its_declaration():
     from test_capi_symbols import _code, _reaches
-    path = os.path.join(ROOT, "inverse-audio-synthesis_amd", "csrc", "tied_kernels.hip")
+    path = os.path.join(ROOT, "inverse-audio-synthesis_amd", "csrc", "match_step_kernels.hip")
     assert _reaches(path, os.path.join(ROOT, "include", "ias_hip_tied.h"), set())
     code = _code(path)
     assert 'extern "C" int ias_match_tied_step(' in code and "getenv" not in code and "ias_diag_env" not in code
+    assert 'extern "C" int ias_match_adam_step(' in code          # the untied step shares the file and its Adam update
+    assert _reaches(path, os.path.join(ROOT, "include", "ias_hip.h"), set())
     makefile = open(os.path.join(ROOT, "inverse-audio-synthesis_amd", "csrc", "Makefile")).read()
     assert "ias_hip_tied.h" in makefile
 
